@@ -12,6 +12,9 @@ JSON). One "step" = ``--requests-per-step`` requests (40 = the reference run).
 ``value`` is the whole-job aggregate (sum over ranks of requests / max wall time).
 
     python bench.py [--gpus N --steps K --warmup W]
+    ... bench.py --dump-outputs DIR  # + the replies of the last timed step as DIR/*.npy (prompts and
+                                     # weights are the same in every run with the same arguments)
+    ... bench.py --full              # + whatever is measured beyond the headline run (nothing yet)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
     ... bench.py --gpus N --tp T   # N/T replicas, each a T-way tensor-parallel engine (RCCL / xGMI):
                                    # rank 0 of each TP group serves HTTP, the others follow its steps
@@ -51,11 +54,14 @@ def pct(xs, p):
 
 
 async def run_load(port: int, n: int, concurrency: int, max_tokens: int, rank: int, start_idx: int,
-                   model: str = "Qwen/Qwen2.5-1.5B-Instruct", api_key: str | None = None, client: str = "lean"):
+                   model: str = "Qwen/Qwen2.5-1.5B-Instruct", api_key: str | None = None, client: str = "lean",
+                   keep_last: int = 0, kept: dict | None = None):
     """Closed loop: ``concurrency`` requests in flight, ``n`` in all (reference bench_load.py:160-212).
     ``client`` "lean" = vgate.utils.http1 keep-alive pool (the default: the load generator shares
     this process's event loop with the server, so its own per-request cost would be charged to
-    the server), "aiohttp" = the reference's client library."""
+    the server), "aiohttp" = the reference's client library. With ``kept`` given, the replies to
+    the last ``keep_last`` requests are stored in it as ``{request index: [completion text,
+    prompt_tokens, completion_tokens]}`` (--dump-outputs)."""
     lat, starts, fails, tokens = [], [], 0, 0
     sem = asyncio.Semaphore(concurrency)
     path = "/v1/chat/completions"
@@ -92,6 +98,9 @@ async def run_load(port: int, n: int, concurrency: int, max_tokens: int, rank: i
                     fails += 1
                 else:
                     tokens += data["usage"]["completion_tokens"]
+                    if kept is not None and i >= n - keep_last:
+                        kept[i] = [data["choices"][0]["message"]["content"], data["usage"]["prompt_tokens"],
+                                   data["usage"]["completion_tokens"]]
             except Exception:  # noqa: BLE001
                 fails += 1
             lat.append(time.perf_counter() - t0)
@@ -166,21 +175,25 @@ async def serve_and_bench(args, rank: int, world: int, dist_ok: bool, client=Non
     per_step = args.requests_per_step
     key = BENCH_KEY if args.security else None
 
-    async def load(n, start_idx):
+    kept = {}  # --dump-outputs: the replies of the last timed step, by request index
+
+    async def load(n, start_idx, keep_last=0):
         if client is None:  # default: the load loop shares this process's event loop / GIL
             return await run_load(port, n, args.concurrency, args.max_tokens, rank, start_idx, args.model, key,
-                                  args.client)
+                                  args.client, keep_last, kept if keep_last else None)
         # the load generator is its own process (as the reference's bench_load.py against a
         # running server): one command line in, one result line out; the server keeps serving
         # on this event loop while the reply is awaited off-loop
         cmd = {"port": port, "n": n, "concurrency": args.concurrency, "max_tokens": args.max_tokens,
-               "rank": rank, "start_idx": start_idx, "model": args.model, "api_key": key, "client": args.client}
+               "rank": rank, "start_idx": start_idx, "model": args.model, "api_key": key, "client": args.client,
+               "keep_last": keep_last}
         client.stdin.write(json.dumps(cmd) + "\n")
         client.stdin.flush()
         line = await asyncio.get_running_loop().run_in_executor(None, client.stdout.readline)
         if not line:
             raise RuntimeError("load client exited")
         r = json.loads(line)
+        kept.update({int(i): v for i, v in r.get("kept", {}).items()})
         return r["lat"], r["fails"], r["tokens"], r["wall"], r.get("starts", [])
 
     # warmup (also captures the hipGraph buckets this load uses)
@@ -228,7 +241,7 @@ async def serve_and_bench(args, rank: int, world: int, dist_ok: bool, client=Non
     rc0 = rcache.hits if rcache is not None else None
     t0 = time.perf_counter()
     mon = asyncio.create_task(lag_monitor(t0))
-    lat, fails, tokens, _, starts = await load(per_step * args.steps, 0)
+    lat, fails, tokens, _, starts = await load(per_step * args.steps, 0, per_step if args.dump_outputs else 0)
     mon.cancel()
     if prof is not None:
         prof.disable()
@@ -298,7 +311,9 @@ async def serve_and_bench(args, rank: int, world: int, dist_ok: bool, client=Non
             "slowest": [[round(st, 3), round(la, 4)] for la, st in slow],
             "loop_lag_max_ms": round(lag["max_ms"], 2), "loop_lag_at_s": round(lag["at_s"], 3),
             "gc_gen2_collections": gcs["n2"], "gc_max_pause_ms": round(gcs["max_ms"], 2),
-            "n": per_step * args.steps, "engine": snap, "wave_trace_ms": trace}
+            "n": per_step * args.steps, "engine": snap, "wave_trace_ms": trace,
+            "outputs": ([kept.get(i) for i in range(per_step * (args.steps - 1), per_step * args.steps)]
+                        if args.dump_outputs else None)}
 
 
 def run_follower(args, rank: int) -> None:
@@ -316,11 +331,46 @@ def client_loop():
     """--client-proc: one JSON load command per stdin line -> one JSON result per stdout line."""
     for line in sys.stdin:
         c = json.loads(line)
+        kept = {}
         lat, fails, tokens, wall, starts = asyncio.run(run_load(c["port"], c["n"], c["concurrency"], c["max_tokens"],
                                                         c["rank"], c["start_idx"], c["model"], c["api_key"],
-                                                        c.get("client", "lean")))
-        sys.stdout.write(json.dumps({"lat": lat, "fails": fails, "tokens": tokens, "wall": wall, "starts": starts}) + "\n")
+                                                        c.get("client", "lean"), c.get("keep_last", 0), kept))
+        sys.stdout.write(json.dumps({"lat": lat, "fails": fails, "tokens": tokens, "wall": wall, "starts": starts,
+                                     "kept": kept}) + "\n")
         sys.stdout.flush()
+
+
+DUMP_LIMIT_BYTES = 48 << 20  # --dump-outputs writes at most this much (float32 elements x 4)
+
+
+def dump_outputs(path: str, rows: list) -> None:
+    """--dump-outputs: what the clients received for the last timed step, one row per request in
+    request order (rank-major): ``completion_text_bytes.npy`` [R, W] (the UTF-8 bytes of
+    ``choices[0].message.content``, padded with -1), ``prompt_tokens.npy`` and
+    ``completion_tokens.npy`` [R] (the reply's ``usage``), all float32. A failed request is a row
+    of -1. Beyond DUMP_LIMIT_BYTES a fixed (seed 0) sample of the rows is written and
+    ``sampled_rows.npy`` names them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    texts = [r[0].encode("utf-8") if r else b"" for r in rows]
+    width = max([1] + [len(t) for t in texts])
+    idx = np.arange(len(rows))
+    fit = max(1, DUMP_LIMIT_BYTES // (4 * (width + 2)))
+    if os.path.exists(os.path.join(path, "sampled_rows.npy")):  # of an earlier, larger run
+        os.remove(os.path.join(path, "sampled_rows.npy"))
+    if len(rows) > fit:
+        idx =np.sort(np.random.default_rng(0).choice(len(rows), size=fit, replace=False))
+        np.save(os.path.join(path, "sampled_rows.npy"), idx.astype(np.float64))
+    width = min(width, DUMP_LIMIT_BYTES // 4 - 2)  # one reply longer than the whole limit: its head
+    text = np.full((len(idx), width), -1.0, dtype=np.float32)
+    for k, i in enumerate(idx):
+        b = np.frombuffer(texts[i][:width], dtype=np.uint8)
+        text[k, :len(b)] = b
+    np.save(os.path.join(path, "completion_text_bytes.npy"), text)
+    np.save(os.path.join(path, "prompt_tokens.npy"),
+            np.array([rows[i][1] if rows[i] else -1 for i in idx], dtype=np.float32))
+    np.save(os.path.join(path, "completion_tokens.npy"),
+            np.array([rows[i][2] if rows[i] else -1 for i in idx], dtype=np.float32))
 
 
 def main():
@@ -329,6 +379,12 @@ def main():
     ap.add_argument("--tp", type=int, default=1, help="tensor-parallel degree of each replica (divides the world)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the replies of the last timed step as DIR/<name>.npy "
+                         "(see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure that take runs of their own "
+                         "(none today: every field of the result line comes from the one timed region)")
     ap.add_argument("--concurrency", type=int, default=8)
     ap.add_argument("--requests-per-step", type=int, default=40)
     ap.add_argument("--max-tokens", type=int, default=64)
@@ -407,6 +463,8 @@ def main():
     else:
         allr = [res]
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [row for r in allr for row in r["outputs"]])
         model_name = args.model.split("/")[-1]
         lat = [x for r in allr for x in r["lat"]]
         total = sum(r["n"] for r in allr)

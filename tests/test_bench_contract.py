@@ -56,6 +56,33 @@ def test_bench_tensor_parallel_two_ranks_cpu(tmp_path):
 
 
 @pytest.mark.timeout(600)
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs DIR: the replies of the LAST timed step (requests-per-step rows, request order) as
+    float32 .npy files; --full is accepted and prints the same single result line."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=str(ROOT), OMP_NUM_THREADS="2", VGATE_DRY_RUN="false")
+    out = tmp_path / "dump"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "tiny",
+           "--max-tokens", "8", "--requests-per-step", "12", "--kv-blocks", "512", "--port", "18345", "--full",
+           "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=540)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert REQUIRED <= set(r) and r["steps"] == 2 and r["failures"] == 0
+    assert sorted(f.name for f in out.iterdir()) == ["completion_text_bytes.npy", "completion_tokens.npy",
+                                                     "prompt_tokens.npy"]
+    text, ct, pt = (np.load(out / f"{n}.npy") for n in ("completion_text_bytes", "completion_tokens", "prompt_tokens"))
+    assert text.dtype == ct.dtype == pt.dtype == np.float32
+    assert text.shape[0] == 12 and ct.shape == pt.shape == (12,)
+    assert (ct >= 1).all() and (ct <= 8).all() and (pt > 0).all()
+    assert ((text >= -1) & (text <= 255)).all() and (text[:, 0] >= 0).all()  # every reply has text
+    # the timed region really ran --steps x --requests-per-step requests
+    assert abs(r["value"] - 24 / (2 * r["ms_per_step"] / 1e3)) / r["value"] < 0.02
+
+
+@pytest.mark.timeout(600)
 def test_bench_forensics_account_for_the_timed_wall(tmp_path):
     """One rank on CPU: the engine thread's timed wall splits into idle + coalesce + busy and that sum
     matches the timed wall; per-step averages and the wave trace are timed-region
