@@ -792,7 +792,7 @@ void dispatch_epi(GemmParams p, const GemmArgs& g, hipStream_t st) {
     if constexpr (!AWQ) {
       if (g.ntb == 4 && ntiles % 4 == 0) { launch_one<1, 4, EPI, 0, AWQ>(p, g, st); return; }
     }
-    if (g.ntb == 2 || (g.ntb == 0 && pair)) launch_one<1, 2, EPI, 0, AWQ>(p, g, st);
+    if ((g.ntb == 2 && ntiles % 2 == 0) || (g.ntb == 0 && pair)) launch_one<1, 2, EPI, 0, AWQ>(p, g, st);
     else launch_one<1, 1, EPI, 0, AWQ>(p, g, st);
     return;
   }
@@ -815,7 +815,7 @@ void dispatch_epi(GemmParams p, const GemmArgs& g, hipStream_t st) {
     if constexpr (!AWQ) {
       if (g.ntb == 4 && ntiles % 4 == 0 && g.M <= 16) { VG_NORM(4); return; }
     }
-    if (g.ntb == 2 || (g.ntb == 0 && pair)) VG_NORM(2);
+    if ((g.ntb == 2 && ntiles % 2 == 0) || (g.ntb == 0 && pair)) VG_NORM(2);  // (odd tile count: one tile per block)
     else VG_NORM(1);
   }
 #undef VG_NORM

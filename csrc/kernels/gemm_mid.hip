@@ -338,8 +338,9 @@ static bool launch_midw_epi(const GemmParams& p, hipStream_t st) {
 
 bool launch_gemm_mid(const GemmArgs& g, hipStream_t st) {
   // (the wide form also takes decode batches, M <= 16: one m-tile, one x phase)
+  // (no RMSNorm hand-off here, producer or consumer: the decode kernels keep those launches)
   if ((g.M <= 16 && g.waves != 8) || g.M > 64 || g.row_idx != nullptr || g.norm_w != nullptr || g.N % 16 != 0 ||
-      g.K % 32 != 0)
+      g.K % 32 != 0 || g.ssp_out != nullptr || g.ssp_in != nullptr)
     return false;
   GemmParams p{};
   p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = nullptr;

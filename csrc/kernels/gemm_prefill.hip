@@ -1004,7 +1004,7 @@ static bool launch_prefill_epi(const GemmParams& p, int force_bn, int force_sk, 
 bool launch_gemm_prefill(const GemmArgs& g, hipStream_t st) {
   if (g.M <= 0) return true;
   const int norm = g.norm_w != nullptr ? 1 : (g.rownorm ? 2 : 0);
-  if (norm == 1) return false;
+  if (norm == 1 || g.ssp_out != nullptr || g.ssp_in != nullptr) return false;  // (no RMSNorm hand-off here)
   GemmParams p{};
   p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = g.row_idx;
   p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;

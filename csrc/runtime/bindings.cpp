@@ -89,6 +89,8 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
   int64_t M = x.size(0);
   const int32_t* ridx = opt_ptr<const int32_t>(row_idx, torch::kInt32, "row_idx");
   if (ridx) M = row_idx->numel();
+  // (the decode kernels load the row index under the f32 epilogue only: gemm_epilogue.h row_of_e)
+  TORCH_CHECK(!ridx || epi == 1, "gemm: row_idx gathers rows for the f32 epilogue only (LM head)");
   const int64_t ncols = (epi == 2) ? N / 2 : N;
   if (epi == 1) CHECK_DT(out, torch::kFloat32); else CHECK_DT(out, torch::kBFloat16);
   if (epi == 3) TORCH_CHECK((N / 16) % 2 == 0, "qkv epilogue needs an even tile count");

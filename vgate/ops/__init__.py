@@ -302,7 +302,8 @@ def linear(x: torch.Tensor, lin: Linear, out: torch.Tensor | None = None,
     sums of out^2 into ssp; prenorm=(ssp, eps) on an AWQ consumer whose x IS that hg applies the
     row scale from ssp (no gamma loads or x^2 pass in the int4 kernel).
 
-    norm=(w, eps): fused RMSNorm of x rows (deferred row scale, see gemm.hip); row_idx: gather rows of x first;
+    norm=(w, eps): fused RMSNorm of x rows (deferred row scale, see gemm.hip); row_idx: gather rows of x first
+    (GPU: with out_f32 only, the LM head's form — the binding rejects it under another epilogue);
     qkv=dict(positions, slots, cos_sin, k_cache, v_cache, hq, hkv): fused bias + RoPE +
     KV write, returns q [M, hq*128] (layout "qkv" only).
     """
