@@ -614,8 +614,6 @@ static int attn_waves(const AttnArgs& a) {
 int g_flash_prefill = -1;  // -1: VGATE_FLASH_PREFILL (default on); 0 / 1: set_flash_prefill (tests)
 void set_flash_prefill(int on) { g_flash_prefill = on; }
 
-static int cu_count();
-
 void launch_attention(const AttnArgs& a, int dec_seqs, hipStream_t st) {
   int tiles = a.num_tiles > 0 ? a.num_tiles : 0;
   // prefill tiles on the flash kernel (its own launch; a decode-only graph bucket carries no tile
@@ -642,7 +640,7 @@ void launch_attention(const AttnArgs& a, int dec_seqs, hipStream_t st) {
       const size_t leaders = (size_t)tiles * 16 / qpb + (size_t)a.S + 1;
       const size_t slots = leaders * a.Hkv * fc.nw;
       const size_t blocks = (size_t)tiles * 16 / qpb * a.Hkv;
-      const size_t cap = (size_t)cu_count() * (fc.ct == 2 ? 1 : 2);
+      const size_t cap = (size_t)cu_count(1) * (fc.ct == 2 ? 1 : 2);
       if (blocks < 2 * cap) zs = 2;
       if (blocks * 4 <= cap) zs = 4;
       if (slots > 32768 || slots * zs * (fc.ct * 4 + 1) * 1024 > f.fl_ws_bytes) zs = 1;
@@ -679,16 +677,6 @@ void launch_attention(const AttnArgs& a, int dec_seqs, hipStream_t st) {
     b.tl = tl_take("attn_reduce", dec_seqs * a.Hq);
     hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(dec_seqs, a.Hq), dim3(128), 0, st, b);
   }
-}
-
-static int cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 1;
-  }();
-  return n;
 }
 
 void launch_attn_decode(const AttnArgs& a, hipStream_t st) {

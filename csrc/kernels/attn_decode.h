@@ -5,7 +5,7 @@
 #pragma once
 #include <type_traits>
 
-#include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace vgate {
 
@@ -569,15 +569,10 @@ static inline bool qa_setup(GemmParams& p, const GemmArgs& g, int gx, int slices
   return true;
 }
 
-template <typename K>
-static void qa_launch(K kern, const GemmParams& p, const AttnArgs& a, const QaSync& q, int waves, size_t lds,
-                      hipStream_t st) {
-  if (lds > 64 * 1024) {
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    (void)attr;
-  }
-  hipLaunchKernelGGL(kern, dim3(q.nprod + a.S * a.num_parts * a.Hkv), dim3(64 * waves), lds, st, p, a, q);
+template <auto Kern>
+static void qa_launch(const GemmParams& p, const AttnArgs& a, const QaSync& q, int waves, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024) allow_dynamic_lds<Kern>(160 * 1024);
+  hipLaunchKernelGGL(Kern, dim3(q.nprod + a.S * a.num_parts * a.Hkv), dim3(64 * waves), lds, st, p, a, q);
 }
 
 }  // namespace vgate

@@ -105,34 +105,13 @@ void launch_awq_dequant(const void* wq, const uint16_t* scales, const uint16_t* 
 
 template <bool AWQ>
 static void launch_dispatch(GemmParams p, const GemmArgs& g, hipStream_t st) {
-  switch (g.epi) {
-    case EPI_SILU: dispatch_epi<EPI_SILU, AWQ>(p, g, st); break;
-    case EPI_QKV: dispatch_epi<EPI_QKV, AWQ>(p, g, st); break;
-    case EPI_F32: dispatch_epi<EPI_F32, AWQ>(p, g, st); break;
-    default: dispatch_epi<EPI_BF16, AWQ>(p, g, st);
-  }
+  with_epi(g.epi, [&](auto e) { dispatch_epi<decltype(e)::value, AWQ>(p, g, st); });
 }
 
-static GemmParams to_params(const GemmArgs& g) {
-  GemmParams p{};
-  p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = g.row_idx;
-  p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;
-  p.norm_w = g.norm_w; p.eps = g.eps;
-  p.bias = g.bias; p.res = g.res; p.ldr = g.ldr;
-  p.out = g.out; p.ldo = g.ldo;
-  p.slabs = g.slabs; p.counters = g.counters;
-  p.gran = nullptr; p.fault = g.fault;  // (granule split-K: set by the decode launchers when it fits)
-  p.positions = g.positions; p.slots = g.slots; p.cos_sin = g.cos_sin;
-  p.k_cache = g.k_cache; p.v_cache = g.v_cache; p.hq = g.hq; p.hkv = g.hkv; p.bs = g.bs;
-  p.scales = g.scales; p.zeros = g.zeros; p.group = g.group; p.szp = g.awq_szp;
-  p.dbg_ts = g.dbg_ts;
-  p.hg = g.hg; p.hg_gamma = g.hg_gamma; p.ssp_out = g.ssp_out; p.ssp_in = g.ssp_in; p.ssn = g.ssn;
-  p.ar = ArFused{};
-  if (g.ar_world > 0) {
-    for (int r = 0; r < 8; ++r) p.ar.base[r] = g.ar_fused[r];
-    p.ar.err = g.ar_err; p.ar.rank = g.ar_rank; p.ar.world = g.ar_world; p.ar.spin = ar_spin();
-  }
-  return p;
+// the tile / decode kernels on the launcher's own heuristic: a declined plan's knobs mean nothing to them
+static void launch_fallback(GemmArgs h, hipStream_t st) {
+  h.path = PATH_AUTO; h.waves = 0; h.splitk = 0; h.ntb = 0;
+  launch_dispatch<false>(gemm_params(h), h, st);
 }
 
 void launch_gemm(const GemmArgs& g, hipStream_t st) {
@@ -140,55 +119,50 @@ void launch_gemm(const GemmArgs& g, hipStream_t st) {
   // TP row-parallel decode GEMM with the all-reduce in the epilogue: the tile-per-block decode kernels
   // (one wave finishes a whole 16-row tile: epilogue_ar's lane layout); the binding checked the shape
   if (g.ar_world > 0) {
-    dispatch_epi<EPI_BF16_AR, false>(to_params(g), g, st);
+    dispatch_epi<EPI_BF16_AR, false>(gemm_params(g), g, st);
+    return;
+  }
+  // mixed prefill + decode steps (16 < M <= 64): the medium-M kernel when the start-up tuner
+  // measured it faster (gemm_mid.hip); it declines shapes / modes it does not take
+  if (g.path == PATH_MID && launch_gemm_mid(g, st)) return;
+  // decode rows on the register-stationary kernel (a decode plan / forced; gemm_kx_bf16.hip)
+  if (g.path == PATH_KX) {
+    GemmArgs h = g;
+    if (h.ntb > NTB_KX_1 || h.ntb < NTB_KX_4) h.ntb = 0;
+    if (!launch_dense_kx(h, st)) launch_fallback(g, st);
+    return;
+  }
+  // decode rows on the stream-K kernel (a decode plan / forced), else the tile-per-block kernels:
+  // declined (shape / mode / occupancy), its plan's (waves, blocks per CU, k-group) fields are dropped
+  if (g.path == PATH_STREAMK) {
+    if (!launch_gemm_sk(g, st)) launch_fallback(g, st);
     return;
   }
   // long steps (prefill chunks): the LDS-tiled MFMA kernel (gemm_prefill.hip) on the same packed
   // weights; it declines shapes / modes it does not take
-  // mixed prefill + decode steps (16 < M <= 64): the medium-M kernel when the start-up tuner
-  // measured it faster (path 2, gemm_mid.hip); it declines shapes / modes it does not take
-  if (g.path == 2 && launch_gemm_mid(g, st)) return;
-  // decode rows on the register-stationary kernel (path 4: a decode plan / forced; gemm_kx_bf16.hip)
-  if (g.path == 4) {
+  if (g.path == PATH_PREFILL || (g.path == PATH_AUTO && g.M >= 128 && g.waves == 0 && g.splitk == 0)) {
     GemmArgs h = g;
-    if (h.ntb > -12 || h.ntb < -14) h.ntb = 0;
-    if (launch_dense_kx(h, st)) return;
-    h.path = 0; h.waves = 0; h.splitk = 0; h.ntb = 0;
-    launch_dispatch<false>(to_params(h), h, st);
-    return;
-  }
-  // decode rows on the stream-K kernel (path 3: a decode plan / forced), else the tile-per-block kernels
-  if (g.path == 3) {
-    if (launch_gemm_sk(g, st)) return;
-    // declined (shape / mode / occupancy): a stream-K plan's (waves, blocks per CU, k-group) fields
-    // mean nothing to the tile kernels — fall back on the launcher's own heuristic
-    GemmArgs h = g;
-    h.path = 0; h.waves = 0; h.splitk = 0; h.ntb = 0;
-    launch_dispatch<false>(to_params(h), h, st);
-    return;
-  }
-  if (g.path == 1 || (g.path == 0 && g.M >= 128 && g.waves == 0 && g.splitk == 0)) {
-    GemmArgs h = g;
-    if (g.path == 0) h.ntb = 0;
+    if (g.path == PATH_AUTO) h.ntb = PT_AUTO;
     if (launch_gemm_prefill(h, st)) return;
   }
-  launch_dispatch<false>(to_params(g), g, st);
+  launch_dispatch<false>(gemm_params(g), g, st);
 }
 
 void launch_awq_gemm(const GemmArgs& g, hipStream_t st) {
   if (g.M <= 0) return;
   if (g.ar_world > 0) {  // fused all-reduce: the K-split int4 kernel (gemm_finish -> epilogue_ar)
     GemmArgs h = g;
-    h.ntb = -2;
-    dispatch_epi<EPI_BF16_AR, true>(to_params(h), h, st);
+    h.ntb = NTB_AWQ_GEMM;
+    dispatch_epi<EPI_BF16_AR, true>(gemm_params(h), h, st);
     return;
   }
   // decode (M <= 16) on the register-stationary int4 kernel: the launcher's choice (no forced waves /
-  // tiles per block), or g.ntb = -12 / -13 / -14 (1 / 2 / 4 tiles per block) with the forced waves / slices
-  if (g.path == 0 && ((g.ntb == 0 && g.waves == 0) || (g.ntb <= -12 && g.ntb >= -14)) && launch_awq_kx(g, st)) return;
-  // mixed prefill + decode steps (16 < M <= 64) on the int4 medium kernel (path 2)
-  if (g.path == 2 && launch_awq_mid(g, st)) return;
-  launch_dispatch<true>(to_params(g), g, st);
+  // tiles per block), or g.ntb = NTB_KX_1 / _2 / _4 (tiles per block) with the forced waves / slices
+  const bool kx_forced = g.ntb <= NTB_KX_1 && g.ntb >= NTB_KX_4;
+  if (g.path == PATH_AUTO && ((g.ntb == 0 && g.waves == 0) || kx_forced) && launch_awq_kx(g, st)) return;
+  // mixed prefill + decode steps (16 < M <= 64) on the int4 medium kernel
+  if (g.path == PATH_MID && launch_awq_mid(g, st)) return;
+  launch_dispatch<true>(gemm_params(g), g, st);
 }
 
 }  // namespace vgate

@@ -2,7 +2,7 @@
 // gemm_awq_kx.hip; longer prompts: the bf16 prefill kernel on a dequantised scratch copy, gemm.hip.)
 #include <algorithm>
 
-#include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace vgate {
 
@@ -187,23 +187,10 @@ __global__ __launch_bounds__(512) void awq_mid_kernel(GemmParams p, int wide) { 
   }
 }
 
-template <int EPI, int NORM, int NTB>
-void launch_prefill_reduce(const GemmParams& p, int nz, hipStream_t st);
-
-static int cu_count_awq() {
-  static const int n = [] {
-    int v = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
-
 template <int EPI, int NORM>
 static bool launch_awq_mid_epi(const GemmParams& p, int force_w, int force_s, size_t slab_bytes, hipStream_t st) {
   const int ntiles = p.N / 16, KQ = p.K / 128, MT = (p.M + 15) / 16, PH = MT == 1 ? 1 : 2;
-  const int ncu = cu_count_awq();
+  const int ncu = cu_count();
   int wide = 0, W = 0, S = 1, nb = 0;
   if (force_w == 8 || (force_w <= 0 && ntiles >= ncu && KQ <= 16 && (ntiles + ncu - 1) / ncu <= 8)) {
     wide = 1;
@@ -228,14 +215,10 @@ static bool launch_awq_mid_epi(const GemmParams& p, int force_w, int force_s, si
   GemmParams q = p;
   if (q.dbg_ts == nullptr) q.dbg_ts = tl_take(wide ? "awq_mid_wide" : "awq_mid", nb * S);
   const dim3 grid(nb, S), block(64 * W);
-#define VG_AM(MT_, Q_)                                                                                 \
-  do {                                                                                                 \
-    auto kern = awq_mid_kernel<MT_, Q_, EPI, NORM>;                                                    \
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) ==  \
-                       hipSuccess;                                                                     \
-    (void)attr;                                                                                        \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, q, wide);                                           \
+#define VG_AM(MT_, Q_)                                                                       \
+  do {                                                                                       \
+    allow_dynamic_lds<awq_mid_kernel<MT_, Q_, EPI, NORM>>(160 * 1024);                       \
+    hipLaunchKernelGGL((awq_mid_kernel<MT_, Q_, EPI, NORM>), grid, block, lds, st, q, wide); \
   } while (0)
 #define VG_AMQ(MT_)                     \
   do {                                  \
@@ -259,31 +242,14 @@ bool launch_awq_mid(const GemmArgs& g, hipStream_t st) {
   if (g.M <= 0 || g.M > 64 || g.awq_szp == nullptr || g.group != 128 || g.N % 16 != 0 || g.K % 128 != 0 ||
       g.rownorm || (g.ssp_in != nullptr && g.norm_w != nullptr) || g.row_idx != nullptr)
     return false;
-  GemmParams p{};
-  p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = nullptr;
-  p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;
-  p.norm_w = g.norm_w; p.eps = g.eps;
-  p.bias = g.bias; p.res = g.res; p.ldr = g.ldr;
-  p.out = g.out; p.ldo = g.ldo;
-  p.splitk = 1;
-  p.slabs = g.slabs;
-  p.positions = g.positions; p.slots = g.slots; p.cos_sin = g.cos_sin;
-  p.k_cache = g.k_cache; p.v_cache = g.v_cache; p.hq = g.hq; p.hkv = g.hkv; p.bs = g.bs;
-  p.szp = g.awq_szp; p.group = g.group;
-  p.dbg_ts = g.dbg_ts;
-  p.hg = g.hg; p.hg_gamma = g.hg_gamma; p.ssp_out = g.ssp_out; p.ssp_in = g.ssp_in; p.ssn = g.ssn;
+  const GemmParams p = gemm_params(g);
   const bool gam = g.norm_w != nullptr, pre = g.ssp_in != nullptr;
-#define VG_AMD(E)                                                                  \
-  return gam ? launch_awq_mid_epi<E, 1>(p, g.waves, g.splitk, g.slab_bytes, st)    \
-       : pre ? launch_awq_mid_epi<E, 3>(p, g.waves, g.splitk, g.slab_bytes, st)    \
-             : launch_awq_mid_epi<E, 0>(p, g.waves, g.splitk, g.slab_bytes, st)
-  switch (g.epi) {
-    case EPI_SILU: VG_AMD(EPI_SILU);
-    case EPI_QKV: VG_AMD(EPI_QKV);
-    case EPI_F32: VG_AMD(EPI_F32);
-    default: VG_AMD(EPI_BF16);
-  }
-#undef VG_AMD
+  return with_epi(g.epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return gam ? launch_awq_mid_epi<E, 1>(p, g.waves, g.splitk, g.slab_bytes, st)
+         : pre ? launch_awq_mid_epi<E, 3>(p, g.waves, g.splitk, g.slab_bytes, st)
+               : launch_awq_mid_epi<E, 0>(p, g.waves, g.splitk, g.slab_bytes, st);
+  });
 }
 
 }  // namespace vgate

@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace vgate {
 
@@ -597,16 +597,6 @@ struct Plan { int waves, splitk; };
 
 extern int g_dec_u;       // gemm.hip: -100 = the launcher's rule; else the forced decode register group size (tests)
 
-inline int cu_count_gemm() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
-
 // Decomposition from the MI355X sweep (benchmarks/micro_gpu.py, M=8, in-graph timing;
 // profiles/r1_gemm_sweep.log): 8 waves per block without split-K is best for the
 // small projections (qkv 3.5 us, o_proj 3.6 us — at the ~1.8 us launch floor plus one
@@ -746,7 +736,7 @@ static void launch_m(GemmParams p, const GemmArgs& g, hipStream_t st) {
     return;
   }
   // (AWQ here: the K-split awq_gemm_kernel — TP ranks with the fused all-reduce, group 64, shapes the
-  // register-stationary kernel declines, gemm_awq_kx.hip; g.ntb = -2 forces it)
+  // register-stationary kernel declines, gemm_kx_q4.hip; g.ntb = NTB_AWQ_GEMM forces it)
   if constexpr (!AWQ) {
     // M > 16: N-split tile kernel with a shared LDS copy of x (see gemm_tile_kernel)
     const int ntiles = g.N / 16;

@@ -330,22 +330,12 @@ static bool kx_qa(GemmParams p, const GemmArgs& g, int groups, int S, int kqs, h
     size_t lds;
     if (!qa_setup(p, g, groups, S, nw, red_bytes<1, 1>(nw) + ssq_bytes<1>(nw) + 16, a, q, lds)) return false;
     if (p.dbg_ts == nullptr) p.dbg_ts = tl_take(Q4 ? "awq_kx_qa" : "kx_qa", q.nprod + a.S * a.num_parts * a.Hkv);
-    if (kqw == 1) qa_launch(kx_qa_kernel<Q4, XP, 1, NORM>, p, a, q, nw, lds, st);
-    else if (kqw == 2) qa_launch(kx_qa_kernel<Q4, XP, 2, NORM>, p, a, q, nw, lds, st);
-    else qa_launch(kx_qa_kernel<Q4, XP, 3, NORM>, p, a, q, nw, lds, st);
+    if (kqw == 1) qa_launch<kx_qa_kernel<Q4, XP, 1, NORM>>(p, a, q, nw, lds, st);
+    else if (kqw == 2) qa_launch<kx_qa_kernel<Q4, XP, 2, NORM>>(p, a, q, nw, lds, st);
+    else qa_launch<kx_qa_kernel<Q4, XP, 3, NORM>>(p, a, q, nw, lds, st);
     *g.fa_done = true;
     return true;
   }
-}
-
-static int kx_cus() {
-  static const int n = [] {
-    int v = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
 }
 
 template <bool Q4, int XP, int KQW, int TMAX, int EPI, int NORM, bool WIDE>
@@ -353,24 +343,20 @@ static bool kx_go(const GemmParams& p, dim3 grid, int nw, hipStream_t st) {
   if (64 * nw > kx_max_threads<Q4, XP, KQW, TMAX, NORM>()) return false;
   const size_t lds = WIDE ? (size_t)nw * TMAX * 1024 + (size_t)nw * 16 * 4 : red_bytes<1, TMAX>(nw) + ssq_bytes<1>(nw) + 16;
   if (lds > 160 * 1024) return false;
-  auto kern = kx_kernel<Q4, XP, KQW, TMAX, EPI, NORM, WIDE>;
-  if (lds > 64 * 1024) {
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    (void)attr;
-  }
+  constexpr auto kern = kx_kernel<Q4, XP, KQW, TMAX, EPI, NORM, WIDE>;
+  if (lds > 64 * 1024) allow_dynamic_lds<kern>(160 * 1024);
   hipLaunchKernelGGL(kern, grid, dim3(64 * nw), lds, st, p);
   return true;
 }
 
 // Grid choice. WIDE when N has at least one tile per CU (and no slices are forced): one block per CU,
-// min(16, K / 128) waves. Otherwise GROUP: TB tiles per block (g.ntb -12 / -13 / -14 force 1 / 2 / 4;
+// min(16, K / 128) waves. Otherwise GROUP: TB tiles per block (g.ntb NTB_KX_1 / _2 / _4 force 1 / 2 / 4;
 // default 1), K slices while the grid still fits the CUs and every slice keeps >= 16 k-quads
 // (down_proj: 96 tiles x 2 slices of 35), min(16, slice) waves. g.waves / g.splitk force the wave /
 // slice counts (sweeps, tests).
 template <bool Q4, int XP, int TB, int EPI, int NORM>
 static bool kx_group(GemmParams p, const GemmArgs& g, hipStream_t st) {
-  const int ntiles = g.N / 16, KQ = g.K / 128, ncu = kx_cus();
+  const int ntiles = g.N / 16, KQ = g.K / 128, ncu = cu_count();
   if (ntiles % TB) return false;
   const int groups = ntiles / TB;
   int S = g.splitk > 0 ? g.splitk : 1;
@@ -424,9 +410,9 @@ static bool kx_group(GemmParams p, const GemmArgs& g, hipStream_t st) {
 
 template <bool Q4, int XP, int EPI, int NORM>
 static bool kx_launch_xp(GemmParams p, const GemmArgs& g, hipStream_t st) {
-  const int ntiles = g.N / 16, KQ = g.K / 128, ncu = kx_cus();
+  const int ntiles = g.N / 16, KQ = g.K / 128, ncu = cu_count();
   if constexpr (EPI != EPI_QKV) {
-    if (ntiles >= ncu && g.splitk <= 1 && g.ntb != -13 && g.ntb != -14) {
+    if (ntiles >= ncu && g.splitk <= 1 && g.ntb != NTB_KX_2 && g.ntb != NTB_KX_4) {
       const int nb = ncu, tneed = (ntiles + nb - 1) / nb;
       const int nw = g.waves > 0 ? g.waves : std::min(16, KQ);
       if (nw > 16) return false;
@@ -441,8 +427,8 @@ static bool kx_launch_xp(GemmParams p, const GemmArgs& g, hipStream_t st) {
       return false;
     }
     if constexpr (NORM == 0) {  // multi-tile GROUP blocks: the plain / residual (+ hand-off producer) GEMMs
-      if (g.ntb == -13) return kx_group<Q4, XP, 2, EPI, NORM>(p, g, st);
-      if (g.ntb == -14) return kx_group<Q4, XP, 4, EPI, NORM>(p, g, st);
+      if (g.ntb == NTB_KX_2) return kx_group<Q4, XP, 2, EPI, NORM>(p, g, st);
+      if (g.ntb == NTB_KX_4) return kx_group<Q4, XP, 4, EPI, NORM>(p, g, st);
     }
   }
   return kx_group<Q4, XP, 1, EPI, NORM>(p, g, st);
@@ -451,23 +437,6 @@ static bool kx_launch_xp(GemmParams p, const GemmArgs& g, hipStream_t st) {
 template <bool Q4, int EPI, int NORM>
 static bool kx_launch(const GemmParams& p, const GemmArgs& g, hipStream_t st) {
   return g.M <= 8 ? kx_launch_xp<Q4, 2, EPI, NORM>(p, g, st) : kx_launch_xp<Q4, 1, EPI, NORM>(p, g, st);
-}
-
-static GemmParams kx_params(const GemmArgs& g) {
-  GemmParams p{};
-  p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = g.row_idx;
-  p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;
-  p.norm_w = g.norm_w; p.eps = g.eps;
-  p.bias = g.bias; p.res = g.res; p.ldr = g.ldr;
-  p.out = g.out; p.ldo = g.ldo;
-  p.splitk = 1; p.slabs = g.slabs; p.counters = g.counters;
-  p.gran = nullptr; p.fault = g.fault;
-  p.positions = g.positions; p.slots = g.slots; p.cos_sin = g.cos_sin;
-  p.k_cache = g.k_cache; p.v_cache = g.v_cache; p.hq = g.hq; p.hkv = g.hkv; p.bs = g.bs;
-  p.szp = g.awq_szp; p.group = g.group;
-  p.dbg_ts = g.dbg_ts;
-  p.hg = g.hg; p.hg_gamma = g.hg_gamma; p.ssp_out = g.ssp_out; p.ssp_in = g.ssp_in; p.ssn = g.ssn;
-  return p;
 }
 
 }  // namespace vgate

@@ -9,7 +9,7 @@ bool launch_dense_kx(const GemmArgs& g, hipStream_t st) {
   if (g.M <= 0 || g.M > 16 || g.N % 16 != 0 || g.K % 128 != 0 || g.norm_w != nullptr || g.ar_world > 0 ||
       g.row_idx != nullptr || g.epi == EPI_F32 || (g.ssp_in != nullptr && g.rownorm))
     return false;
-  const GemmParams p = kx_params(g);
+  const GemmParams p = gemm_params(g);
   const int norm = g.rownorm ? 2 : g.ssp_in != nullptr ? 3 : 0;
 #define VG_KX(E)                                               \
   return norm == 2 ? kx_launch<false, E, 2>(p, g, st)          \

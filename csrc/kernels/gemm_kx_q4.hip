@@ -7,7 +7,7 @@ bool launch_awq_kx(const GemmArgs& g, hipStream_t st) {
   if (g.M <= 0 || g.M > 16 || g.awq_szp == nullptr || g.group != 128 || g.N % 16 != 0 || g.K % 128 != 0 ||
       g.rownorm || g.ar_world > 0 || (g.ssp_in != nullptr && g.norm_w != nullptr) || g.epi == EPI_F32)
     return false;
-  const GemmParams p = kx_params(g);
+  const GemmParams p = gemm_params(g);
   const int norm = g.norm_w != nullptr ? 1 : g.ssp_in != nullptr ? 3 : 0;
 #define VG_KX(E)                                              \
   return norm == 1 ? kx_launch<true, E, 1>(p, g, st)          \

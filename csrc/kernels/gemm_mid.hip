@@ -24,19 +24,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace vgate {
-
-static int cu_count_mid() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    return v > 0 ? v : 256;
-  }();
-  return n;
-}
 
 template <int MT, int KS, int EPI, int NORM>
 __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p) {
@@ -254,24 +244,16 @@ __global__ __launch_bounds__(1024) void gemm_midw_kernel(GemmParams p) {
   }
 }
 
-// defined in gemm_prefill.hip (split-K combine + epilogue, shared with the prefill kernels)
-template <int EPI, int NORM, int NTB>
-void launch_prefill_reduce(const GemmParams& p, int nz, hipStream_t st);
-
 template <int MT, int EPI, int NORM>
 static void launch_mid_mt(const GemmParams& p, int W, int S, int ks, hipStream_t st) {
   const dim3 grid(p.N / 16 / W, S), block(64 * W);
   const size_t lds = (size_t)ks * MT * 1024;
   GemmParams q = p;
   if (q.dbg_ts == nullptr) q.dbg_ts = tl_take("gemm_mid", (int)(grid.x * grid.y));
-#define VG_MID(K_)                                                                         \
-  do {                                                                                     \
-    auto kern = gemm_mid_kernel<MT, K_, EPI, NORM>;                                        \
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),            \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                           K_ * MT * 1024) == hipSuccess;                  \
-    (void)attr;                                                                            \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, q);                                     \
+#define VG_MID(K_)                                                                     \
+  do {                                                                                 \
+    allow_dynamic_lds<gemm_mid_kernel<MT, K_, EPI, NORM>>(K_ * MT * 1024);             \
+    hipLaunchKernelGGL((gemm_mid_kernel<MT, K_, EPI, NORM>), grid, block, lds, st, q); \
   } while (0)
   if (ks <= 8) VG_MID(8);
   else if (ks <= 12) VG_MID(12);
@@ -311,7 +293,7 @@ static bool launch_mid_epi(const GemmParams& p, int force_w, int force_s, size_t
 template <int EPI, int NORM>
 static bool launch_midw_epi(const GemmParams& p, hipStream_t st) {
   const int ntiles = p.N / 16, KT = p.K / 32, KP = (KT + 15) / 16;
-  const int nb = std::min(ntiles, cu_count_mid());
+  const int nb = std::min(ntiles, cu_count());
   const int tmax = (ntiles + nb - 1) / nb;
   if (KT > 64 || KP * tmax > 16 || ntiles < nb) return false;
   const int MT = (p.M + 15) / 16;
@@ -319,14 +301,10 @@ static bool launch_midw_epi(const GemmParams& p, hipStream_t st) {
   const size_t lds = std::max<size_t>((size_t)KT * (MT == 1 ? 1 : 2) * 1024, (size_t)KP * tmax * MT * (1024 + 64));
   GemmParams q = p;
   if (q.dbg_ts == nullptr) q.dbg_ts = tl_take("gemm_midw", nb);
-#define VG_MW(P_)                                                                                      \
-  do {                                                                                                 \
-    auto kern = gemm_midw_kernel<P_, EPI, NORM>;                                                       \
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) ==  \
-                       hipSuccess;                                                                     \
-    (void)attr;                                                                                        \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, q);                                                 \
+#define VG_MW(P_)                                                                   \
+  do {                                                                              \
+    allow_dynamic_lds<gemm_midw_kernel<P_, EPI, NORM>>(160 * 1024);                 \
+    hipLaunchKernelGGL((gemm_midw_kernel<P_, EPI, NORM>), grid, block, lds, st, q); \
   } while (0)
   if (MT == 1) VG_MW(1);
   else if (MT == 2) VG_MW(2);
@@ -342,29 +320,14 @@ bool launch_gemm_mid(const GemmArgs& g, hipStream_t st) {
   if ((g.M <= 16 && g.waves != 8) || g.M > 64 || g.row_idx != nullptr || g.norm_w != nullptr || g.N % 16 != 0 ||
       g.K % 32 != 0 || g.ssp_out != nullptr || g.ssp_in != nullptr)
     return false;
-  GemmParams p{};
-  p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = nullptr;
-  p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;
-  p.norm_w = nullptr; p.eps = g.eps;
-  p.bias = g.bias; p.res = g.res; p.ldr = g.ldr;
-  p.out = g.out; p.ldo = g.ldo;
-  p.splitk = 1;
-  p.slabs = g.slabs;
-  p.positions = g.positions; p.slots = g.slots; p.cos_sin = g.cos_sin;
-  p.k_cache = g.k_cache; p.v_cache = g.v_cache; p.hq = g.hq; p.hkv = g.hkv; p.bs = g.bs;
-  p.dbg_ts = g.dbg_ts;
+  const GemmParams p = gemm_params(g);
   const int norm = g.rownorm ? 2 : 0;
-#define VG_MD(E)                                                                             \
-  if (g.waves == 8) return norm == 2 ? launch_midw_epi<E, 2>(p, st) : launch_midw_epi<E, 0>(p, st); \
-  return norm == 2 ? launch_mid_epi<E, 2>(p, g.waves, g.splitk, g.slab_bytes, st)           \
-                   : launch_mid_epi<E, 0>(p, g.waves, g.splitk, g.slab_bytes, st)
-  switch (g.epi) {
-    case EPI_SILU: VG_MD(EPI_SILU);
-    case EPI_QKV: VG_MD(EPI_QKV);
-    case EPI_F32: VG_MD(EPI_F32);
-    default: VG_MD(EPI_BF16);
-  }
-#undef VG_MD
+  return with_epi(g.epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (g.waves == 8) return norm == 2 ? launch_midw_epi<E, 2>(p, st) : launch_midw_epi<E, 0>(p, st);
+    return norm == 2 ? launch_mid_epi<E, 2>(p, g.waves, g.splitk, g.slab_bytes, st)
+                     : launch_mid_epi<E, 0>(p, g.waves, g.splitk, g.slab_bytes, st);
+  });
 }
 
 }  // namespace vgate

@@ -22,7 +22,7 @@
 // column panel run back to back on one XCD (one HBM read of the panel per XCD L2).
 #include <cstdlib>
 
-#include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace vgate {
 
@@ -764,7 +764,7 @@ __global__ __launch_bounds__(256) void prefill_reduce_kernel(GemmParams p, int n
   epilogue<NTB, EPI, false>(p, v, m, nt0, nsub, EpiPre<NTB>{}, m < p.M);
 }
 
-// the combine launch for p.splitk-free callers (gemm_mid.hip)
+// the combine launch (declared in gemm_host.h: gemm_mid.hip and gemm_awq_mid.hip share it)
 template <int EPI, int NORM, int NTB>
 void launch_prefill_reduce(const GemmParams& p, int nz, hipStream_t st) {
   const int groups = ((p.M + 15) / 16) * (p.N / (16 * NTB));
@@ -781,76 +781,55 @@ VG_RED_INST(EPI_SILU)
 VG_RED_INST(EPI_QKV)
 #undef VG_RED_INST
 
-template <int EPI, int NORM, int NTB, int BM = 256, int BN = 128, int WM = 4, int WN = 2, int NS = 3, int SCHED = 0,
-          int KS = 2>
-static void launch_prefill2_one(const GemmParams& p, int nz, hipStream_t st) {
-  constexpr int STAGE = (BN / 16 + BM / 16) * KS * 1024;
-  const int blocks = ((p.M + BM - 1) / BM) * (p.N / BN);
+constexpr int PF_NTB = 1;  // every epilogue works on self-contained 16-column tiles
+
+// One tile grid of `blocks` tiles x nz K slices: the timeline slot, the LDS opt-in (above the 64 KiB
+// a kernel gets unasked), the launch, then the combine of the slices
+template <auto Kern, int EPI, int NORM>
+static void launch_tile_grid(const char* name, const GemmParams& p, int blocks, int nz, int threads, int lds,
+                             hipStream_t st) {
   GemmParams q = p;
-  if (q.dbg_ts == nullptr) q.dbg_ts = tl_take("gemm_prefill2", blocks * nz);
-  auto kern = gemm_prefill2_kernel<BM, BN, WM, WN, NS, EPI, NORM, NTB, SCHED, KS>;
-  static bool attr = [&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               NS * STAGE) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL(kern, dim3(blocks, nz), dim3(64 * WM * WN), NS * STAGE, st, q);
-  if (nz > 1) {
-    const int groups = ((p.M + 15) / 16) * (p.N / (16 * NTB));
-    GemmParams r = p;
-    r.dbg_ts = tl_take("prefill_reduce", (groups + 3) / 4);
-    hipLaunchKernelGGL((prefill_reduce_kernel<EPI, NORM, NTB>), dim3((groups + 3) / 4), dim3(256), 0, st, r, nz);
-  }
+  if (q.dbg_ts == nullptr) q.dbg_ts = tl_take(name, blocks * nz);
+  if (lds > 64 * 1024) allow_dynamic_lds<Kern>(lds);
+  hipLaunchKernelGGL(Kern, dim3(blocks, nz), dim3(threads), lds, st, q);
+  if (nz > 1) launch_prefill_reduce<EPI, NORM, PF_NTB>(p, nz, st);
 }
 
-template <int EPI, int NORM, int NTB, int BM = 256, int BN = 128, int WM = 4, int WN = 2, int NS = 3, int KS = 2>
-static void launch_prefill2_cfg(const GemmParams& p, int nz, hipStream_t st) {
-  // MFMAs at raised priority (schedule 1): +5-7 % on the 256 x 256 tile, neutral on 256 x 128; the
-  // split DMA issue was neutral to negative (profiles/r2_prefill_gemm_sched.log)
-  launch_prefill2_one<EPI, NORM, NTB, BM, BN, WM, WN, NS, 1, KS>(p, nz, st);
+template <int EPI, int NORM, int BM, int BN>
+static void launch_prefill1(const GemmParams& p, int nz, hipStream_t st) {
+  constexpr int LDS = 2 * (BN / 16 + BM / 16) * 2 * 1024;
+  launch_tile_grid<gemm_prefill_kernel<BM, BN, EPI, NORM, PF_NTB>, EPI, NORM>(
+      "gemm_prefill", p, ((p.M + BM - 1) / BM) * (p.N / BN), nz, 256, LDS, st);
 }
 
-template <int EPI, int NORM, int NTB, int BN = 256>
-static void launch_prefill4_cfg(const GemmParams& p, int nz, hipStream_t st) {
-  constexpr int STAGE = (BN / 16 + 16) * 2 * 1024;
-  const int blocks = ((p.M + 255) / 256) * (p.N / BN);
-  GemmParams q = p;
-  if (q.dbg_ts == nullptr) q.dbg_ts = tl_take("gemm_prefill4", blocks * nz);
-  auto kern = gemm_prefill4_kernel<BN, EPI, NORM, NTB>;
-  constexpr int LDS = 2 * STAGE + P4_ROWSS + 1024;  // ring + the folded norm's row sums
-  static bool attr = [&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               LDS) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL(kern, dim3(blocks, nz), dim3(512), LDS, st, q);
-  if (nz > 1) {
-    const int groups = ((p.M + 15) / 16) * (p.N / (16 * NTB));
-    GemmParams r = p;
-    r.dbg_ts = tl_take("prefill_reduce", (groups + 3) / 4);
-    hipLaunchKernelGGL((prefill_reduce_kernel<EPI, NORM, NTB>), dim3((groups + 3) / 4), dim3(256), 0, st, r, nz);
-  }
+// WM x WN waves on an NS-deep ring of 64-deep stages (KS = 2), MFMAs at raised priority (schedule 1):
+// +5-7 % on the 256 x 256 tile, neutral on 256 x 128; the split DMA issue was neutral to negative
+// (profiles/r2_prefill_gemm_sched.log)
+template <int EPI, int NORM, int BM, int BN, int WM, int WN, int NS>
+static void launch_prefill2(const GemmParams& p, int nz, hipStream_t st) {
+  constexpr int KS = 2, LDS = NS * (BN / 16 + BM / 16) * KS * 1024;
+  launch_tile_grid<gemm_prefill2_kernel<BM, BN, WM, WN, NS, EPI, NORM, PF_NTB, 1, KS>, EPI, NORM>(
+      "gemm_prefill2", p, ((p.M + BM - 1) / BM) * (p.N / BN), nz, 64 * WM * WN, LDS, st);
 }
 
-static int cu_count() {
-  static const int n = [] {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      c = 0;
-    return c;
-  }();
-  return n;
+template <int BN>
+constexpr int p4_lds() {
+  return 2 * (BN / 16 + 16) * 2 * 1024 + P4_ROWSS + 1024;  // ring + the folded norm's row sums
+}
+
+template <int EPI, int NORM, int BN>
+static void launch_prefill4(const GemmParams& p, int nz, hipStream_t st) {
+  launch_tile_grid<gemm_prefill4_kernel<BN, EPI, NORM, PF_NTB>, EPI, NORM>(
+      "gemm_prefill4", p, ((p.M + 255) / 256) * (p.N / BN), nz, 512, p4_lds<BN>(), st);
 }
 
 // persistent 4-phase kernel (whole rounds + the K-split tail), one block per CU; slices = the tail's K
 // slices (0: G / R, at least 4 K-tiles each, at most 8). false = not taken (no tail to split, no
-// tickets / slot room)
-template <int EPI, int NORM, int NTB, int BN>
-static bool launch_prefill4sk_cfg(const GemmParams& p, int slices, int max_counters, size_t slab_bytes,
-                                  hipStream_t st) {
-  constexpr int STAGE = (BN / 16 + 16) * 2 * 1024;
+// tickets / slot room, CU count unknown)
+template <int EPI, int NORM, int BN>
+static bool launch_prefill4sk(const GemmParams& p, int slices, int max_counters, size_t slab_bytes, hipStream_t st) {
   const int tiles = ((p.M + 255) / 256) * (p.N / BN);
-  const int G = cu_count();
+  const int G = cu_count(0);
   if (G <= 0 || p.counters == nullptr || p.slabs == nullptr) return false;
   const int R = tiles % G, KT = p.K / 64;
   if (R == 0) return false;  // whole rounds: the tile grid is the same schedule
@@ -863,30 +842,75 @@ static bool launch_prefill4sk_cfg(const GemmParams& p, int slices, int max_count
   if (S < 1 || R > max_counters || (size_t)R * (S - 1) * p4sk_slot_floats<BN>() * 4 > slab_bytes) return false;
   GemmParams q = p;
   if (q.dbg_ts == nullptr) q.dbg_ts = tl_take("gemm_prefill4sk", G);
-  auto kern = gemm_prefill4sk_kernel<BN, EPI, NORM, NTB>;
-  constexpr int LDS = 2 * STAGE + P4_ROWSS + 1024;  // ring + the folded norm's row sums
-  static bool attr = [&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               LDS) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL(kern, dim3(G), dim3(512), LDS, st, q, tiles, S);
+  constexpr auto kern = gemm_prefill4sk_kernel<BN, EPI, NORM, PF_NTB>;
+  allow_dynamic_lds<kern>(p4_lds<BN>());
+  hipLaunchKernelGGL(kern, dim3(G), dim3(512), p4_lds<BN>(), st, q, tiles, S);
   return true;
 }
 
-template <int BM, int BN, int EPI, int NORM, int NTB>
-static void launch_prefill_cfg(const GemmParams& p, int nz, hipStream_t st) {
-  constexpr int STAGE = (BN / 16 + BM / 16) * 2 * 1024;
-  const int blocks = ((p.M + BM - 1) / BM) * (p.N / BN);
-  GemmParams q = p;
-  if (q.dbg_ts == nullptr) q.dbg_ts = tl_take("gemm_prefill", blocks * nz);
-  hipLaunchKernelGGL((gemm_prefill_kernel<BM, BN, EPI, NORM, NTB>), dim3(blocks, nz), dim3(256), 2 * STAGE, st, q);
-  if (nz > 1) {
-    const int groups = ((p.M + 15) / 16) * (p.N / (16 * NTB));
-    GemmParams r = p;
-    r.dbg_ts = tl_take("prefill_reduce", (groups + 3) / 4);
-    hipLaunchKernelGGL((prefill_reduce_kernel<EPI, NORM, NTB>), dim3((groups + 3) / 4), dim3(256), 0, st, r, nz);
-  }
+// ---- the forced tiles (GemmArgs::ntb under PATH_PREFILL, launchers.h PrefillTile) ----
+struct PrefillCall {
+  const GemmParams& p;
+  int nz;        // K slices of a tile grid (forced, else the launcher's choice)
+  int force_sk;  // the persistent kernels: the tail's K slices (0 = the launcher's choice)
+  int max_counters;
+  size_t slab_bytes;
+  hipStream_t st;
+};
+struct PrefillRow {
+  int code;
+  int ndiv;  // N must be a multiple (else the launch is declined)
+  void (*launch)(const PrefillCall&);
+};
+
+template <int EPI, int NORM, int BM, int BN>
+static void pf_v1(const PrefillCall& c) { launch_prefill1<EPI, NORM, BM, BN>(c.p, c.nz, c.st); }
+template <int EPI, int NORM>
+static void pf_v1_by_n(const PrefillCall& c) {  // 128 x 128 where N allows
+  if (c.p.N % 128 == 0) pf_v1<EPI, NORM, 128, 128>(c);
+  else pf_v1<EPI, NORM, 128, 64>(c);
+}
+template <int EPI, int NORM, int BM, int BN, int WM, int WN, int NS>
+static void pf_v2(const PrefillCall& c) { launch_prefill2<EPI, NORM, BM, BN, WM, WN, NS>(c.p, c.nz, c.st); }
+template <int EPI, int NORM, int BN>
+static void pf_v4(const PrefillCall& c) { launch_prefill4<EPI, NORM, BN>(c.p, c.nz, c.st); }
+template <int EPI, int NORM, int BN>
+static void pf_v4sk(const PrefillCall& c) {  // declined -> the tile grid, one slice
+  if (!launch_prefill4sk<EPI, NORM, BN>(c.p, c.force_sk, c.max_counters, c.slab_bytes, c.st))
+    launch_prefill4<EPI, NORM, BN>(c.p, 1, c.st);
+}
+
+template <int EPI, int NORM>
+static const PrefillRow* prefill_row(int code) {
+  static const PrefillRow rows[] = {
+      // the 2-deep-ring kernel, 256 threads
+      {PT_128x64, 64, pf_v1<EPI, NORM, 128, 64>},
+      {PT_128x128, 64, pf_v1_by_n<EPI, NORM>},
+      // 256-row tiles over 4 x 2 waves: 3-deep ring, and 256 x 256 on a 2-deep ring (sweeps / tests)
+      {PT_256x128, 128, pf_v2<EPI, NORM, 256, 128, 4, 2, 3>},
+      {PT_256x256, 256, pf_v2<EPI, NORM, 256, 256, 4, 2, 2>},
+      // the 4-phase kernel, and its persistent forms with a K-split tail (start-up tuner candidates)
+      {PT_P4_256x128, 128, pf_v4<EPI, NORM, 128>},
+      {PT_P4_256x256, 256, pf_v4<EPI, NORM, 256>},
+      {PT_P4SK_256x128, 128, pf_v4sk<EPI, NORM, 128>},
+      {PT_P4SK_256x256, 256, pf_v4sk<EPI, NORM, 256>},
+      // mid-M (128 < M <= 512) tuner candidates: the 128-row tiles on a 4-deep ring, one block per CU
+      // (the 2-deep ring above waits vmcnt(0) per K-tile and relies on a second resident block)
+      {PT_128x128_R2x2, 128, pf_v2<EPI, NORM, 128, 128, 2, 2, 4>},
+      {PT_128x128_R2x4, 128, pf_v2<EPI, NORM, 128, 128, 2, 4, 4>},
+      {PT_128x64_R2x2, 64, pf_v2<EPI, NORM, 128, 64, 2, 2, 4>},
+      {PT_128x64_R4x2, 64, pf_v2<EPI, NORM, 128, 64, 4, 2, 4>},
+      // wide-N mid-M tiles that fill the chip where the 256- / 128-row tiles leave CUs idle or waste rows
+      // (gate_up at 448 rows: 256 x 256 covers 140 of 256 CUs, 128-row tiles make 280 blocks): 64 x 512
+      // over 8 waves (448 rows: 7 x 35 = 245 blocks, no padded rows) and 128 x 320 over 8 waves (224);
+      // the same tiles with 32-deep stages on 4-deep rings measured 15-30 % slower warm and cold
+      // (profiles/r5_prefill_wide_tiles_sweep.log)
+      {PT_64x512, 512, pf_v2<EPI, NORM, 64, 512, 1, 8, 2>},
+      {PT_128x320, 320, pf_v2<EPI, NORM, 128, 320, 2, 4, 2>},
+  };
+  for (const PrefillRow& r : rows)
+    if (r.code == code) return &r;
+  return nullptr;
 }
 
 // Split-K partials leave with non-temporal stores: dirty fp32 slabs in L2 are written back at the
@@ -899,12 +923,11 @@ static void launch_prefill_cfg(const GemmParams& p, int nz, hipStream_t st) {
 template <int EPI, int NORM>
 static bool launch_prefill_epi(const GemmParams& p, int force_bn, int force_sk, size_t slab_bytes, int max_counters,
                                hipStream_t st) {
-  constexpr int NTB = 1;  // every epilogue works on self-contained 16-column tiles
   if (p.K % 64 != 0 || p.N % 64 != 0 || p.row_idx != nullptr) return false;
   const int mb = (p.M + 127) / 128;
   bool wide = p.N % 128 == 0 && mb * (p.N / 128) >= 240;
-  if (force_bn == 128) wide = p.N % 128 == 0;
-  if (force_bn == 64) wide = false;
+  if (force_bn == PT_128x128) wide = p.N % 128 == 0;
+  if (force_bn == PT_128x64) wide = false;
   const int blocks = mb * (p.N / (wide ? 128 : 64));
   int nz = 1;
   if (force_sk > 0) {
@@ -917,87 +940,31 @@ static bool launch_prefill_epi(const GemmParams& p, int force_bn, int force_sk, 
   while (nz > 1 && nk / nz < 4) --nz;
   const size_t need = ((size_t)nz * p.M * p.N + (size_t)nz * p.M) * 4;
   if (nz > 1 && (p.slabs == nullptr || need > slab_bytes)) nz = 1;
-  // 256 x 256 when its grid covers ~3/4 of the chip, else v2 (256 x 128, 3-deep ring)
-  // when its grid still covers the chip without split-K (profiles/r2_prefill_gemm_sched.log: the
-  // 256-square tile +20-35 % at >= 192 blocks, up to -30 % at 128)
-  const int blocks_v3 = ((p.M + 255) / 256) * (p.N % 256 == 0 ? p.N / 256 : 0);
-  const int blocks_v2 = ((p.M + 255) / 256) * (p.N % 128 == 0 ? p.N / 128 : 0);
-  if (force_bn == 0 && force_sk == 0 && blocks_v3 >= 180) {
-    // the 4-phase 256 x 256 kernel (v4: +7-22 % over the same tile with one barrier per K-tile,
-    // profiles/r2_prefill_gemm_v4.log)
-    launch_prefill4_cfg<EPI, NORM, NTB>(p, 1, st);
+  const PrefillCall c{p, nz, force_sk, max_counters, slab_bytes, st};
+  if (const PrefillRow* row = prefill_row<EPI, NORM>(force_bn)) {
+    if (p.N % row->ndiv != 0) return false;
+    row->launch(c);
     return true;
   }
-  if (force_bn == 0 && force_sk == 0 && blocks_v2 >= 192) {
-    // the 4-phase kernel on 256 x 128 (+0-8 % over the 3-deep-ring v2 at 192-256 blocks,
-    // profiles/r2_prefill_gemm_v4.log)
-    launch_prefill4_cfg<EPI, NORM, NTB, 128>(p, 1, st);
-    return true;
+  if (force_bn == PT_AUTO && force_sk == 0) {
+    // the 4-phase kernel (v4: +7-22 % over the same tile with one barrier per K-tile,
+    // profiles/r2_prefill_gemm_v4.log): 256 x 256 when its grid covers ~3/4 of the chip, else 256 x 128
+    // when its grid still covers the chip without split-K (+0-8 % over the 3-deep-ring v2 at 192-256
+    // blocks; profiles/r2_prefill_gemm_sched.log: the 256-square tile +20-35 % at >= 192 blocks, up to
+    // -30 % at 128)
+    const int blocks_v3 = ((p.M + 255) / 256) * (p.N % 256 == 0 ? p.N / 256 : 0);
+    const int blocks_v2 = ((p.M + 255) / 256) * (p.N % 128 == 0 ? p.N / 128 : 0);
+    if (blocks_v3 >= 180) {
+      launch_prefill4<EPI, NORM, 256>(p, 1, st);
+      return true;
+    }
+    if (blocks_v2 >= 192) {
+      launch_prefill4<EPI, NORM, 128>(p, 1, st);
+      return true;
+    }
   }
-  if (force_bn == 256) {  // forced (tests / sweeps), split-K as chosen above
-    if (p.N % 128 != 0) return false;
-    launch_prefill2_cfg<EPI, NORM, NTB>(p, nz, st);
-    return true;
-  }
-  if (force_bn == 512) {  // 256 x 256 block tile, 8 waves of 64 (m) x 128 (n), 2-deep ring (sweeps)
-    if (p.N % 256 != 0) return false;
-    launch_prefill2_cfg<EPI, NORM, NTB, 256, 256, 4, 2, 2>(p, nz, st);
-    return true;
-  }
-  if (force_bn == 1024) {  // v4: the 4-phase 256 x 256 kernel (sweeps / tests)
-    if (p.N % 256 != 0) return false;
-    launch_prefill4_cfg<EPI, NORM, NTB>(p, nz, st);
-    return true;
-  }
-  // persistent forms of the 4-phase kernel, K-split tail (start-up tuner candidates; force_sk = the
-  // tail's K slices); declined -> the tile grid
-  if (force_bn == 1025) {
-    if (p.N % 256 != 0) return false;
-    if (!launch_prefill4sk_cfg<EPI, NORM, NTB, 256>(p, force_sk, max_counters, slab_bytes, st))
-      launch_prefill4_cfg<EPI, NORM, NTB>(p, 1, st);
-    return true;
-  }
-  if (force_bn == 769) {
-    if (p.N % 128 != 0) return false;
-    if (!launch_prefill4sk_cfg<EPI, NORM, NTB, 128>(p, force_sk, max_counters, slab_bytes, st))
-      launch_prefill4_cfg<EPI, NORM, NTB, 128>(p, 1, st);
-    return true;
-  }
-  if (force_bn == 768) {  // v4 on a 256 x 128 tile (sweeps / tests)
-    if (p.N % 128 != 0) return false;
-    launch_prefill4_cfg<EPI, NORM, NTB, 128>(p, nz, st);
-    return true;
-  }
-  // mid-M (128 < M <= 512) tuner candidates: the 128-row tiles on a 4-deep ring, one block per CU
-  // (the 2-deep ring above waits vmcnt(0) per K-tile and relies on a second resident block)
-  if (force_bn == 1280 || force_bn == 1281) {
-    if (p.N % 128 != 0) return false;
-    if (force_bn == 1280) launch_prefill2_cfg<EPI, NORM, NTB, 128, 128, 2, 2, 4>(p, nz, st);
-    else launch_prefill2_cfg<EPI, NORM, NTB, 128, 128, 2, 4, 4>(p, nz, st);
-    return true;
-  }
-  // wide-N mid-M tiles that fill the chip where the 256- / 128-row tiles leave CUs idle or waste rows
-  // (gate_up at 448 rows: 256 x 256 covers 140 of 256 CUs, 128-row tiles make 280 blocks): 64 x 512
-  // over 8 waves (448 rows: 7 x 35 = 245 blocks, no padded rows) and 128 x 320 over 8 waves (224)
-  if (force_bn == 2560) {
-    if (p.N % 512 != 0) return false;
-    launch_prefill2_cfg<EPI, NORM, NTB, 64, 512, 1, 8, 2>(p, nz, st);
-    return true;
-  }
-  if (force_bn == 2561) {
-    if (p.N % 320 != 0) return false;
-    launch_prefill2_cfg<EPI, NORM, NTB, 128, 320, 2, 4, 2>(p, nz, st);
-    return true;
-  }
-  // (the same tiles with 32-deep stages on 4-deep rings measured 15-30 % slower warm and cold:
-  // profiles/r5_prefill_wide_tiles_sweep.log)
-  if (force_bn == 640 || force_bn == 641) {
-    if (force_bn == 640) launch_prefill2_cfg<EPI, NORM, NTB, 128, 64, 2, 2, 4>(p, nz, st);
-    else launch_prefill2_cfg<EPI, NORM, NTB, 128, 64, 4, 2, 4>(p, nz, st);
-    return true;
-  }
-  if (wide) launch_prefill_cfg<128, 128, EPI, NORM, NTB>(p, nz, st);
-  else launch_prefill_cfg<128, 64, EPI, NORM, NTB>(p, nz, st);
+  if (wide) pf_v1<EPI, NORM, 128, 128>(c);
+  else pf_v1<EPI, NORM, 128, 64>(c);
   return true;
 }
 
@@ -1005,30 +972,12 @@ bool launch_gemm_prefill(const GemmArgs& g, hipStream_t st) {
   if (g.M <= 0) return true;
   const int norm = g.norm_w != nullptr ? 1 : (g.rownorm ? 2 : 0);
   if (norm == 1 || g.ssp_out != nullptr || g.ssp_in != nullptr) return false;  // (no RMSNorm hand-off here)
-  GemmParams p{};
-  p.x = g.x; p.lda = g.lda; p.M = g.M; p.row_idx = g.row_idx;
-  p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;
-  p.norm_w = nullptr; p.eps = g.eps;
-  p.bias = g.bias; p.res = g.res; p.ldr = g.ldr;
-  p.out = g.out; p.ldo = g.ldo;
-  p.splitk = 1;
-  p.slabs = g.slabs;
-  p.counters = g.counters; p.fault = g.fault;
-  p.positions = g.positions; p.slots = g.slots; p.cos_sin = g.cos_sin;
-  p.k_cache = g.k_cache; p.v_cache = g.v_cache; p.hq = g.hq; p.hkv = g.hkv; p.bs = g.bs;
-  p.dbg_ts = g.dbg_ts;
-  const int fb = g.ntb;      // reused as the forced tile width (0 = heuristic, 64 / 128)
-  const int fs = g.splitk;   // forced K slices (0 = heuristic)
-#define VG_PF(E)                                                                                         \
-  return norm == 2 ? launch_prefill_epi<E, 2>(p, fb, fs, g.slab_bytes, g.max_counters, st)               \
-                   : launch_prefill_epi<E, 0>(p, fb, fs, g.slab_bytes, g.max_counters, st)
-  switch (g.epi) {
-    case EPI_SILU: VG_PF(EPI_SILU);
-    case EPI_QKV: VG_PF(EPI_QKV);
-    case EPI_F32: VG_PF(EPI_F32);
-    default: VG_PF(EPI_BF16);
-  }
-#undef VG_PF
+  const GemmParams p = gemm_params(g);
+  return with_epi(g.epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return norm == 2 ? launch_prefill_epi<E, 2>(p, g.ntb, g.splitk, g.slab_bytes, g.max_counters, st)
+                     : launch_prefill_epi<E, 0>(p, g.ntb, g.splitk, g.slab_bytes, g.max_counters, st);
+  });
 }
 
 }  // namespace vgate

@@ -355,7 +355,7 @@ bool sk_fits(K kern, int threads, size_t lds, int G) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(kern), threads, lds) !=
       hipSuccess)
     return false;
-  return (long long)per * cu_count_gemm() >= G;
+  return (long long)per * cu_count() >= G;
 }
 
 template <int W, int UA, int EPI, int NORM, int XP>
@@ -364,10 +364,8 @@ bool sk_launch_cfg(const GemmParams& p, const SkParams& s, int nga, int G, int p
   const size_t lds = std::max(need, per_cu == 1 ? (size_t)82 * 1024 : (size_t)54 * 1024);
 #define VG_SK(N)                                                                                              \
   do {                                                                                                        \
-    auto kern = gemm_sk_kernel<W, UA, N, EPI, NORM, XP>;                                                      \
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess; \
-    (void)attr;                                                                                               \
+    constexpr auto kern = gemm_sk_kernel<W, UA, N, EPI, NORM, XP>;                                            \
+    allow_dynamic_lds<kern>(96 * 1024);                                                                       \
     static int fits[3] = {-1, -1, -1}; /* per blocks-per-CU setting (lds and G follow from it) */            \
     if (fits[per_cu] < 0) fits[per_cu] = sk_fits(kern, 64 * W, lds, G) ? 1 : 0;                               \
     if (!fits[per_cu]) return false;                                                                          \
@@ -411,34 +409,21 @@ bool launch_gemm_sk(const GemmArgs& g, hipStream_t st) {
   // sweeps: g.waves 4 = 4 waves per block, g.ntb 4 = groups of 4 k-steps, g.splitk 2 = 2 blocks per CU
   const int W = g.waves == 4 ? 4 : 8, UA = (g.ntb == 4 && W == 8) ? 4 : 8;
   const int per_cu = g.splitk == 2 ? 2 : 1;
-  const int G = cu_count_gemm() * per_cu;
+  const int G = cu_count() * per_cu;
   const int ntiles = g.N / 16, KT = g.K / 32;
   const SkPlan pl = sk_plan(ntiles, KT, g.M, G, W, UA);
   if (!pl.ok) return false;
   if ((size_t)ntiles * (pl.cmax - 1) * 64 * 3 * 16 > g.sk_bytes) return false;
-  GemmParams p{};
-  p.x = reinterpret_cast<const bf16_t*>(g.x); p.lda = g.lda; p.M = g.M;
-  p.wp = reinterpret_cast<const uint4*>(g.wp); p.N = g.N; p.K = g.K;
-  p.eps = g.eps;
-  p.bias = reinterpret_cast<const bf16_t*>(g.bias); p.res = reinterpret_cast<const bf16_t*>(g.res); p.ldr = g.ldr;
-  p.out = g.out; p.ldo = g.ldo;
-  p.splitk = 1;
-  p.positions = g.positions; p.slots = g.slots; p.cos_sin = g.cos_sin;
-  p.k_cache = reinterpret_cast<bf16_t*>(g.k_cache); p.v_cache = reinterpret_cast<bf16_t*>(g.v_cache);
-  p.hq = g.hq; p.hkv = g.hkv; p.bs = g.bs;
+  GemmParams p = gemm_params(g);
   // timeline names by role (benchmarks/timeline.py groups launches by name)
   const char* tl_name = g.epi == EPI_QKV ? "gemm_sk_qkv" : g.epi == EPI_SILU ? "gemm_sk_gate_up"
                         : g.epi == EPI_F32 ? "gemm_sk_f32" : (g.K > g.N ? "gemm_sk_down" : "gemm_sk_o");
   p.dbg_ts = g.dbg_ts != nullptr ? g.dbg_ts : tl_take(tl_name, G);
   SkParams s{KT, ntiles * KT / pl.XP, pl.cmax, reinterpret_cast<uint4*>(g.sk_pub), g.fault};
-#define VG_SKE(E, NORM_) sk_launch<E, NORM_>(p, s, pl.XP, W, UA, pl.NGA, G, per_cu, st)
-  switch (g.epi) {
-    case EPI_SILU: return VG_SKE(EPI_SILU, 2);
-    case EPI_QKV: return VG_SKE(EPI_QKV, 2);
-    case EPI_F32: return VG_SKE(EPI_F32, 0);
-    default: return VG_SKE(EPI_BF16, 0);
-  }
-#undef VG_SKE
+  return with_epi(g.epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return sk_launch<E, (E == EPI_SILU || E == EPI_QKV) ? 2 : 0>(p, s, pl.XP, W, UA, pl.NGA, G, per_cu, st);
+  });
 }
 
 }  // namespace vgate

@@ -9,6 +9,41 @@ namespace vgate {
 
 struct AttnArgs;
 
+// GemmArgs::path: the kernel family a plan / test asks for (a family that declines falls back)
+enum GemmPath : int {
+  PATH_NEVER = -1,   // tile / decode kernels only
+  PATH_AUTO = 0,     // the launcher's rule (dense: the prefill kernels at M >= 128; AWQ: kx at M <= 16)
+  PATH_PREFILL = 1,  // LDS-tiled prefill kernels (gemm_prefill.hip)
+  PATH_MID = 2,      // medium-M kernels (gemm_mid.hip / gemm_awq_mid.hip)
+  PATH_STREAMK = 3,  // stream-K decode kernel (gemm_streamk.hip)
+  PATH_KX = 4,       // register-stationary dense decode kernel (gemm_kx_bf16.hip)
+};
+// GemmArgs::ntb under PATH_PREFILL: the forced block tile (gemm_prefill.hip PrefillTiles; a code in no
+// row of that table runs the heuristic 128-row tiles). R<WM>x<WN>: gemm_prefill2's wave layout on a
+// 4-deep ring; P4: the 4-phase kernel; P4SK: its persistent form with a K-split tail.
+enum PrefillTile : int {
+  PT_AUTO = 0,
+  PT_128x64 = 64,
+  PT_128x128 = 128,  // 128 x 64 when N % 128 != 0
+  PT_256x128 = 256,
+  PT_256x256 = 512,
+  PT_128x64_R2x2 = 640,
+  PT_128x64_R4x2 = 641,
+  PT_P4_256x128 = 768,
+  PT_P4SK_256x128 = 769,
+  PT_P4_256x256 = 1024,
+  PT_P4SK_256x256 = 1025,
+  PT_128x128_R2x2 = 1280,
+  PT_128x128_R2x4 = 1281,
+  PT_64x512 = 2560,
+  PT_128x320 = 2561,
+};
+// GemmArgs::ntb, negative codes of the decode launchers
+constexpr int NTB_AWQ_GEMM = -2;  // AWQ: the K-split awq_gemm kernel, not the kx / mid kernels
+constexpr int NTB_KX_1 = -12;     // kx GROUP form with 1 / 2 / 4 tiles per block
+constexpr int NTB_KX_2 = -13;
+constexpr int NTB_KX_4 = -14;
+
 struct GemmArgs {
   const uint16_t* x;  // [M, K] bf16, row stride lda (rows gathered through row_idx if set)
   int lda;
@@ -28,9 +63,15 @@ struct GemmArgs {
   int epi;            // 0 bf16, 1 f32, 2 silu*mul (gate/up tiles interleaved), 3 qkv+rope+kv-write
   int waves;          // 0 = heuristic
   int splitk;         // 0 = heuristic
-  int ntb;            // 16-column tiles per block for plain / f32 epilogues (0 = heuristic; 1, 2, 4)
-  int path;           // M > 16 dense: 0 auto (prefill kernel at M >= 128), 1 force prefill kernel,
-                      // 2 medium-M kernel (16 < M <= 64), -1 never (tile / decode kernels)
+  // ntb, by the kernel family that takes the launch (0 = that family's heuristic everywhere):
+  //   tile / decode kernels (PATH_AUTO / PATH_NEVER, and every fallback): 16-column tiles per block,
+  //     1 / 2 / 4; AWQ: NTB_AWQ_GEMM keeps the launch on awq_gemm, NTB_KX_1 / _2 / _4 = kx tiles per block
+  //   PATH_KX: NTB_KX_1 / _2 / _4 = kx tiles per block (anything else: the kx launcher's choice)
+  //   PATH_PREFILL: a PrefillTile code
+  //   PATH_STREAMK: 4 = register groups of 4 k-steps (default 8)
+  //   PATH_MID: unused
+  int ntb;
+  int path;           // GemmPath
   float* slabs;       // split-K fp32 partial slabs (workspace) or null
   size_t slab_bytes;
   uint32_t* counters; // split-K arrival tickets, zero-initialised, self-resetting
@@ -82,7 +123,7 @@ void launch_gemm(const GemmArgs& g, hipStream_t st);
 // stream per CU; returns false (nothing launched) for a shape / mode it does not take
 bool launch_gemm_sk(const GemmArgs& g, hipStream_t st);
 // LDS-tiled prefill GEMM (gemm_prefill.hip) for long steps; returns false for a shape / mode it
-// does not take (caller falls back). g.ntb: forced tile width (0 heuristic, 64, 128).
+// does not take (caller falls back). g.ntb: a PrefillTile code, g.splitk: forced K slices.
 bool launch_gemm_prefill(const GemmArgs& g, hipStream_t st);
 // medium-M GEMM (gemm_mid.hip, 16 < M <= 64): W = g.waves tiles per block, g.splitk K slices
 // (0 = heuristic); returns false for a shape / mode it does not take (caller falls back)

@@ -43,11 +43,11 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(GemmParams p, AttnArgs a,
 template <int NORM>
 static bool qa_dispatch(int u, int xp, const GemmParams& p, const AttnArgs& a, const QaSync& q, int waves,
                         size_t lds, hipStream_t st) {
-  if (xp == 4 && u == 8) { qa_launch(qkv_attn_kernel<8, 4, NORM>, p, a, q, waves, lds, st); return true; }
-  if (xp == 2 && u == 6) { qa_launch(qkv_attn_kernel<6, 2, NORM>, p, a, q, waves, lds, st); return true; }
-  if (xp == 2 && u == 8) { qa_launch(qkv_attn_kernel<8, 2, NORM>, p, a, q, waves, lds, st); return true; }
-  if (xp == 1 && u == 6) { qa_launch(qkv_attn_kernel<6, 1, NORM>, p, a, q, waves, lds, st); return true; }
-  if (xp == 1 && u == 8) { qa_launch(qkv_attn_kernel<8, 1, NORM>, p, a, q, waves, lds, st); return true; }
+  if (xp == 4 && u == 8) { qa_launch<qkv_attn_kernel<8, 4, NORM>>(p, a, q, waves, lds, st); return true; }
+  if (xp == 2 && u == 6) { qa_launch<qkv_attn_kernel<6, 2, NORM>>(p, a, q, waves, lds, st); return true; }
+  if (xp == 2 && u == 8) { qa_launch<qkv_attn_kernel<8, 2, NORM>>(p, a, q, waves, lds, st); return true; }
+  if (xp == 1 && u == 6) { qa_launch<qkv_attn_kernel<6, 1, NORM>>(p, a, q, waves, lds, st); return true; }
+  if (xp == 1 && u == 8) { qa_launch<qkv_attn_kernel<8, 1, NORM>>(p, a, q, waves, lds, st); return true; }
   return false;
 }
 

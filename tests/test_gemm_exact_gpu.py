@@ -112,8 +112,8 @@ class Guarded:
                                  f"{rc[:6].tolist()} of {tuple(self.big.shape)} (view starts at row {X.GUARD})")
 
 
-def launches(fn) -> list[str]:
-    """The timeline names of the launches ``fn`` makes."""
+def launches(fn) -> list[tuple]:
+    """The timeline entries (name, offset, blocks) of the launches ``fn`` makes."""
     C = ops.native()
     buf = torch.zeros(1 << 17, dtype=torch.int64, device=DEV)
     C.timeline_start(buf)
@@ -126,7 +126,7 @@ def launches(fn) -> list[str]:
         raise
     finally:
         C.timeline_stop()
-    return [e[0] for e in C.timeline_entries()]
+    return C.timeline_entries()
 
 
 def assert_exact(got: torch.Tensor, want: torch.Tensor, what: str) -> None:
@@ -219,7 +219,8 @@ def launch(p: X.Problem, lin: ops.Linear, mode: str, knobs: dict, twice: bool = 
         C.gemm(xg.view, lin.wp, N, K, og.view, epi, **kw)
 
     fault0 = int(ops.fault_word(DEV)[0])
-    r["names"] = launches(go)
+    ents = launches(go)
+    r["names"], r["blocks"] = [e[0] for e in ents], [e[2] for e in ents]
     what = f"{mode} {knobs} {r['names']}"
     for name, b in bufs.items():
         b.assert_guards(f"{what}: {name}")
@@ -249,7 +250,7 @@ def launch(p: X.Problem, lin: ops.Linear, mode: str, knobs: dict, twice: bool = 
     return r
 
 
-def run_exact(s, mode: str, names: list, twice: bool = False, **knobs) -> None:
+def run_exact(s, mode: str, names: list, twice: bool = False, **knobs) -> dict:
     p, lin = lin_for(s)
     r = launch(p, lin, mode, knobs, twice)
     what = f"{s} {mode} {knobs}"
@@ -262,6 +263,7 @@ def run_exact(s, mode: str, names: list, twice: bool = False, **knobs) -> None:
     if mode == "qkv":  # written slots, skipped tokens and untouched blocks in one comparison
         assert torch.equal(r["k_cache"].cpu().double(), p.exp["k_cache"]), what + " k_cache"
         assert torch.equal(r["v_cache"].cpu().double(), p.exp["v_cache"]), what + " v_cache"
+    return r
 
 
 def run_sensitive(s, names: list, **knobs) -> None:
@@ -282,7 +284,7 @@ def run_sensitive(s, names: list, **knobs) -> None:
 
 
 # ------------------------------------------------------------------ the case matrix
-Case = namedtuple("Case", "id N K knobs names declined")
+Case = namedtuple("Case", "id N K knobs names declined tile")
 TILE_NAME = {"f32": "gemm_f32", "gather": "gemm_f32", "silu": "gemm_gate_up", "qkv": "gemm_qkv"}
 
 
@@ -291,10 +293,10 @@ def tile_name(mode: str) -> str:
     return TILE_NAME.get(mode, "gemm")
 
 
-def case(id, N, K, names=None, declined=False, **knobs):
+def case(id, N, K, names=None, declined=False, tile=None, **knobs):
     """names: the launches the case means to hit; declined: the family does not take this N (the test
-    then asserts the fallback's name instead)."""
-    return Case(id, N, K, knobs, names, declined)
+    then asserts the fallback's name instead); tile: the (BM, BN) block tile of a prefill tile code."""
+    return Case(id, N, K, knobs, names, declined, tile)
 
 
 def takes(c, mode: str, heads_only: bool = False) -> bool:
@@ -600,27 +602,27 @@ PRE_MODES = ["bias", "res", "inplace", "f32", "silu", "qkv"]
 RED = "prefill_reduce"
 PRE_CASES = [
     case("auto", 512, 512, names=["gemm_prefill", RED], path=1),
-    case("t64", 512, 512, names=["gemm_prefill"], path=1, ntb=64, splitk=1),
-    case("t64_s3", 576, 1536, names=["gemm_prefill", RED], path=1, ntb=64, splitk=3),
-    case("t128", 512, 512, names=["gemm_prefill"], path=1, ntb=128, splitk=1),
-    case("t128_n576", 576, 512, names=["gemm_prefill"], path=1, ntb=128, splitk=1),  # (runs 128 x 64 tiles)
-    case("t256_s3", 512, 1536, names=["gemm_prefill2", RED], path=1, ntb=256, splitk=3),
-    case("t256_s3_k2048", 512, 2048, names=["gemm_prefill2", RED], path=1, ntb=256, splitk=3),
+    case("t64", 512, 512, names=["gemm_prefill"], tile=(128, 64), path=1, ntb=64, splitk=1),
+    case("t64_s3", 576, 1536, names=["gemm_prefill", RED], tile=(128, 64), path=1, ntb=64, splitk=3),
+    case("t128", 512, 512, names=["gemm_prefill"], tile=(128, 128), path=1, ntb=128, splitk=1),
+    case("t128_n576", 576, 512, names=["gemm_prefill"], tile=(128, 64), path=1, ntb=128, splitk=1),  # (runs 128 x 64 tiles)
+    case("t256_s3", 512, 1536, names=["gemm_prefill2", RED], tile=(256, 128), path=1, ntb=256, splitk=3),
+    case("t256_s3_k2048", 512, 2048, names=["gemm_prefill2", RED], tile=(256, 128), path=1, ntb=256, splitk=3),
     # declined: N = 576 is no multiple of 128 -> the K-split tile kernel; N = 16 x 37 of no tile at all
     case("t256_n576", 576, 512, path=1, ntb=256, splitk=1, declined=True),
     case("t64_odd", ODD_N, 512, path=1, ntb=64, splitk=1, declined=True),
-    case("t512", 512, 512, names=["gemm_prefill2"], path=1, ntb=512, splitk=1),
-    case("t1024", 512, 512, names=["gemm_prefill4"], path=1, ntb=1024, splitk=1),
-    case("t1024_s3", 512, 1536, names=["gemm_prefill4", RED], path=1, ntb=1024, splitk=3),
-    case("t768", 640, 512, names=["gemm_prefill4"], path=1, ntb=768, splitk=1),
-    case("t1025_tail", 512, 512, names=["gemm_prefill4sk"], path=1, ntb=1025),
-    case("t769_tail_k2048", 640, 2048, names=["gemm_prefill4sk"], path=1, ntb=769),
-    case("t1280", 512, 512, names=["gemm_prefill2"], path=1, ntb=1280, splitk=1),
-    case("t1281_s2_k2048", 512, 2048, names=["gemm_prefill2", RED], path=1, ntb=1281, splitk=2),
-    case("t640", 576, 512, names=["gemm_prefill2"], path=1, ntb=640, splitk=1),
-    case("t641", 576, 512, names=["gemm_prefill2"], path=1, ntb=641, splitk=1),
-    case("t2560", 512, 512, names=["gemm_prefill2"], path=1, ntb=2560, splitk=1),
-    case("t2561", 640, 512, names=["gemm_prefill2"], path=1, ntb=2561, splitk=1),
+    case("t512", 512, 512, names=["gemm_prefill2"], tile=(256, 256), path=1, ntb=512, splitk=1),
+    case("t1024", 512, 512, names=["gemm_prefill4"], tile=(256, 256), path=1, ntb=1024, splitk=1),
+    case("t1024_s3", 512, 1536, names=["gemm_prefill4", RED], tile=(256, 256), path=1, ntb=1024, splitk=3),
+    case("t768", 640, 512, names=["gemm_prefill4"], tile=(256, 128), path=1, ntb=768, splitk=1),
+    case("t1025_tail", 512, 512, names=["gemm_prefill4sk"], tile=(256, 256), path=1, ntb=1025),
+    case("t769_tail_k2048", 640, 2048, names=["gemm_prefill4sk"], tile=(256, 128), path=1, ntb=769),
+    case("t1280", 512, 512, names=["gemm_prefill2"], tile=(128, 128), path=1, ntb=1280, splitk=1),
+    case("t1281_s2_k2048", 512, 2048, names=["gemm_prefill2", RED], tile=(128, 128), path=1, ntb=1281, splitk=2),
+    case("t640", 576, 512, names=["gemm_prefill2"], tile=(128, 64), path=1, ntb=640, splitk=1),
+    case("t641", 576, 512, names=["gemm_prefill2"], tile=(128, 64), path=1, ntb=641, splitk=1),
+    case("t2560", 512, 512, names=["gemm_prefill2"], tile=(64, 512), path=1, ntb=2560, splitk=1),
+    case("t2561", 640, 512, names=["gemm_prefill2"], tile=(128, 320), path=1, ntb=2561, splitk=1),
 ]
 register(PRE_CASES, PRE_M, PRE_MODES, heads_only=True)
 
@@ -629,10 +631,21 @@ register(PRE_CASES, PRE_M, PRE_MODES, heads_only=True)
 @pytest.mark.parametrize("M", PRE_M)
 def test_prefill(M, c, mode):
     """gemm_prefill / gemm_prefill2 / gemm_prefill4 / gemm_prefill4sk (+ prefill_reduce under a forced K
-    split); 129 and 200 rows leave a partial last m-tile of every tile height (64 / 128 / 256)."""
+    split); 129 and 200 rows leave a partial last m-tile of every tile height (64 / 128 / 256). The name
+    alone cannot tell the tile codes of one kernel apart (gemm_prefill2 has seven geometries): a forced
+    code's grid must be ceil(M / BM) * (N / BN) tiles times the forced K slices, the persistent kernel's
+    one block per CU."""
     names = [tile_name(mode)] if c.declined else c.names
     twice = is_twice(c.knobs) or "4sk" in names[0] or RED in names
-    run_exact(spec_for(mode, M, c.N, c.K), mode, names, twice=twice, **c.knobs)
+    s = spec_for(mode, M, c.N, c.K)
+    r = run_exact(s, mode, names, twice=twice, **c.knobs)
+    if c.tile is not None:
+        bm, bn = c.tile
+        nz = max(c.knobs.get("splitk", 0), 1)
+        want = (torch.cuda.get_device_properties(0).multi_processor_count if "4sk" in names[0]
+                else -(-M // bm) * (lin_for(s)[0].N // bn) * nz)
+        assert r["blocks"][0] == want, (f"{c.id} {mode} M={M}: {names[0]} ran {r['blocks'][0]} blocks, "
+                                        f"tile {c.tile} x {nz} slices means {want}")
 
 
 # ---- one sensitivity case per family
