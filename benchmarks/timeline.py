@@ -7,6 +7,7 @@ launch's first block — i.e. how much of the step is kernel bodies and how much
 boundaries / dispatch / drain, which rocprof's per-kernel durations cannot separate.
 
     python benchmarks/timeline.py [--batch 8] [--steps 4] [--json out.json]
+    python benchmarks/timeline.py --penalised      # every row with penalties: the processor step's graph
 """
 from __future__ import annotations
 
@@ -45,7 +46,12 @@ def main():
                     help="after the measured step, replay its graph N times back to back (no host sync between) "
                          "and report the last replay too: a hole that only the first replay shows is the host's "
                          "graph launch, not the GPU")
+    ap.add_argument("--penalised", action="store_true",
+                    help="every request carries repetition / presence / frequency penalties and a logit_bias: the "
+                         "measured step is a processor step (forward + logits kernel + sampler, ModelRunner.proc_graphs)")
     a = ap.parse_args()
+    pen = dict(repetition_penalty=1.1, presence_penalty=0.5, frequency_penalty=0.5,
+               logit_bias={7: 1.0, 11: -1.0}) if a.penalised else {}
     eng = LLMEngine(EngineConfig(model=a.model, device="cuda:0", max_model_len=2048, max_num_seqs=a.max_seqs,
                                  max_num_batched_tokens=2048, num_kv_blocks=a.kv_blocks or None, warmup=False,
                                  quantization=a.quantization))
@@ -53,7 +59,7 @@ def main():
     for i in range(a.batch):
         ids = [100 + (i * 131 + j * 17) % 5000 for j in range(a.ctx)]
         eng.add_request(f"r{i}", prompt_ids=ids,
-                        params=SamplingParams(temperature=0.7, top_p=0.9, max_tokens=400, ignore_eos=True))
+                        params=SamplingParams(temperature=0.7, top_p=0.9, max_tokens=400, ignore_eos=True, **pen))
     eng._drain_inbox()
     for _ in range(0 if a.prefill else 4):  # prefill + a few decode steps (graphs of the decode bucket captured)
         eng.step()
@@ -67,7 +73,8 @@ def main():
                         params=SamplingParams(temperature=0.7, top_p=0.9, max_tokens=1))
         eng._drain_inbox()
     summary, live, cap, t = measure(eng, a.replays)
-    summary.update(batch=a.batch, ctx=a.ctx, replays=a.replays)
+    summary.update(batch=a.batch, ctx=a.ctx, replays=a.replays, penalised=a.penalised,
+                   proc_steps=eng.runner.proc_steps)
     print(json.dumps(summary), flush=True)
     for x in live[:14]:
         print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in x.items() if k not in ("t0", "t1")}))
@@ -82,11 +89,12 @@ def measure(eng, replays: int = 0):
     C = ops.native()
     r = eng.runner
     torch.cuda.synchronize()
-    keys = list(r.graphs.keys())
+    graphs = r.proc_graphs if r.proc_graphs else r.graphs  # processor steps replay their own table
+    keys = list(graphs.keys())
     buf = torch.zeros(1 << 22, dtype=torch.int64, device="cuda")
     C.timeline_start(buf)
     for k in keys:  # re-capture the decode buckets with timeline slots
-        del r.graphs[k]
+        del graphs[k]
     eng.step()
     used = C.timeline_stop()
     ents = C.timeline_entries()
@@ -94,7 +102,7 @@ def measure(eng, replays: int = 0):
         eng.step()
     torch.cuda.synchronize()
     if replays > 0:
-        g = r.graphs[max(r.graphs.keys())]
+        g = graphs[max(graphs.keys())]
         for _ in range(replays):
             g.replay()
         torch.cuda.synchronize()

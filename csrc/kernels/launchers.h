@@ -289,6 +289,14 @@ constexpr int SAMPLE_GRAN_ROW = 2 * SAMPLE_GRAN_SEGS * 2;   // uint4 per row: [p
 constexpr int SAMPLE_WS_GRAN = 256;                         // int32 offset of the granules (16-B aligned)
 constexpr int SAMPLE_WS_WORDS = SAMPLE_WS_GRAN + SAMPLE_GRAN_ROWS * SAMPLE_GRAN_ROW * 4;
 void launch_sample(const SampleArgs& s, hipStream_t st);
+
+// Logits processors, in place on the S sampled rows before launch_sample (logits_proc.hip): row r's
+// unique-token entries {tok, cnt (bit 31 = in prompt), bias, pad} are ent[row_off[r], row_off[r + 1])
+// (clamped to nent), par[4 r] = {rep, inv_rep, pres, freq}, pend[r] = 0 or -(slot + 1) of the
+// sequence's in-flight token in prev[nprev] (prev null: no pending tokens).
+void launch_logits_process(float* logits, int ldl, int S, int V, const int32_t* row_off, const int32_t* pend,
+                           const float* par, const void* ent, int nent, const int32_t* prev, int nprev,
+                           hipStream_t st);
 int sample_segments(int B, int V);
 void set_sample_nseg(int n);  // cap on segments per row, 1..SAMPLE_GRAN_SEGS (1 = one block per row)
 

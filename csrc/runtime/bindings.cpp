@@ -480,6 +480,33 @@ void sample(const Tensor& logits, const c10::optional<Tensor>& temperature,
   vgate::launch_sample(s, cur_stream());
 }
 
+// Penalties + logit_bias on the sampled rows, in place (vgate/runtime/logits_proc.py ProcMeta views).
+void process_logits(Tensor& logits, const Tensor& row_off, const Tensor& pend, const Tensor& par,
+                    const Tensor& entries, const c10::optional<Tensor>& prev) {
+  CHECK_DEV(logits); CHECK_DEV(row_off); CHECK_DEV(pend); CHECK_DEV(par); CHECK_DEV(entries);
+  CHECK_DT(logits, torch::kFloat32); CHECK_DT(row_off, torch::kInt32); CHECK_DT(pend, torch::kInt32);
+  CHECK_DT(par, torch::kFloat32); CHECK_DT(entries, torch::kInt32);
+  CHECK_LASTDIM(logits);
+  TORCH_CHECK(logits.dim() == 2, "process_logits: logits [S, V]");
+  const int64_t S = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(row_off.is_contiguous() && pend.is_contiguous() && par.is_contiguous() && entries.is_contiguous(),
+              "process_logits: contiguous metadata");
+  TORCH_CHECK(row_off.numel() >= S + 1 && pend.numel() >= S && par.numel() >= 4 * S,
+              "process_logits: row_off [S + 1], pend [S], par [S, 4]");
+  TORCH_CHECK(entries.dim() == 2 && entries.size(1) == 4, "process_logits: entries int32 [N, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(entries.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(par.data_ptr()) % 16 == 0,
+              "process_logits: entries and par must be 16-B aligned");
+  const int32_t* pv = opt_ptr<int32_t>(prev, torch::kInt32, "prev");
+  const int nprev = pv != nullptr ? (int)prev->numel() : 0;
+  TORCH_CHECK(pv == nullptr || (prev->is_contiguous() && nprev > 0), "process_logits: prev must be contiguous");
+  c10::DeviceGuard guard(logits.device());
+  vgate::launch_logits_process(reinterpret_cast<float*>(logits.data_ptr()), (int)logits.stride(0), (int)S, (int)V,
+                               reinterpret_cast<const int32_t*>(row_off.data_ptr()),
+                               reinterpret_cast<const int32_t*>(pend.data_ptr()),
+                               reinterpret_cast<const float*>(par.data_ptr()), entries.data_ptr(), (int)entries.size(0),
+                               pv, nprev, cur_stream());
+}
+
 // Warm the memory-side cache with a tensor's bytes (default-policy read sweep, nothing written).
 // Copy the first `nbytes` (rounded up to 16, within both tensors) between a pinned host tensor and
 // a device tensor with a kernel on the current stream (no SDMA engine hand-off, see elementwise.hip).
@@ -663,6 +690,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("logits"), py::arg("temperature"), py::arg("top_p"), py::arg("top_k"), py::arg("seeds"),
         py::arg("offsets"), py::arg("out"), py::arg("out_logprob") = py::none(), py::arg("ws") = py::none(),
         py::arg("fault") = py::none());
+  m.def("process_logits", &process_logits, "repetition / presence / frequency penalties + logit_bias, in place",
+        py::arg("logits"), py::arg("row_off"), py::arg("pend"), py::arg("par"), py::arg("entries"),
+        py::arg("prev") = py::none());
   m.def("sample_segments", &vgate::sample_segments, "blocks per row the sampler uses for (B, V)");
   m.def("set_sample_nseg", &vgate::set_sample_nseg, "cap the sampler's segments per row (1 = one block per row)");
   m.attr("SAMPLE_WS_WORDS") = vgate::SAMPLE_WS_WORDS;

@@ -111,10 +111,18 @@ def _headers(api_key: Optional[str]) -> dict:
     return h
 
 
-def _chat_req(model, messages, temperature, top_p, max_tokens, stream=False) -> dict:
-    return ChatCompletionRequest(model=model, messages=[ChatMessage(**m) for m in messages],
+_CONTROLS = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias", "seed", "top_k")
+
+
+def _chat_req(model, messages, temperature, top_p, max_tokens, stream=False, **controls) -> dict:
+    """Request body; an optional sampling control that was not given does not appear in it."""
+    given = {k: v for k, v in controls.items() if v is not None}
+    if "logit_bias" in given:  # JSON object keys: decimal token ids
+        given["logit_bias"] = {str(k): float(v) for k, v in given["logit_bias"].items()}
+    body = ChatCompletionRequest(model=model, messages=[ChatMessage(**m) for m in messages],
                                  temperature=temperature, top_p=top_p, max_tokens=max_tokens,
-                                 stream=stream).model_dump()
+                                 stream=stream, **given).model_dump()
+    return {k: v for k, v in body.items() if k not in _CONTROLS or k in given}
 
 
 class SyncChatStream:
@@ -163,14 +171,25 @@ class _SyncChat:
         self._c = client
 
     def create(self, *, model: str, messages: list[dict], temperature: float = 0.7, top_p: float = 0.9,
-               max_tokens: int = 256) -> ChatCompletion:
+               max_tokens: int = 256, presence_penalty: Optional[float] = None,
+               frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+               logit_bias: Optional[dict] = None, seed: Optional[int] = None,
+               top_k: Optional[int] = None) -> ChatCompletion:
         data = self._c._request("POST", "/v1/chat/completions",
-                                json=_chat_req(model, messages, temperature, top_p, max_tokens))
+                                json=_chat_req(model, messages, temperature, top_p, max_tokens,
+                                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                                               repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k))
         return ChatCompletion.model_validate(data)
 
     def stream(self, *, model: str, messages: list[dict], temperature: float = 0.7, top_p: float = 0.9,
-               max_tokens: int = 256) -> SyncChatStream:
-        return SyncChatStream(self._c._stream(_chat_req(model, messages, temperature, top_p, max_tokens, True)))
+               max_tokens: int = 256, presence_penalty: Optional[float] = None,
+               frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+               logit_bias: Optional[dict] = None, seed: Optional[int] = None,
+               top_k: Optional[int] = None) -> SyncChatStream:
+        return SyncChatStream(self._c._stream(_chat_req(
+            model, messages, temperature, top_p, max_tokens, True,
+            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+            repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k)))
 
 
 class _SyncEmbeddings:
@@ -263,15 +282,26 @@ class _AsyncChat:
         self._c = client
 
     async def create(self, *, model: str, messages: list[dict], temperature: float = 0.7, top_p: float = 0.9,
-                     max_tokens: int = 256) -> ChatCompletion:
+                     max_tokens: int = 256, presence_penalty: Optional[float] = None,
+                     frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                     logit_bias: Optional[dict] = None, seed: Optional[int] = None,
+                     top_k: Optional[int] = None) -> ChatCompletion:
         data = await self._c._request("POST", "/v1/chat/completions",
-                                      json=_chat_req(model, messages, temperature, top_p, max_tokens))
+                                      json=_chat_req(model, messages, temperature, top_p, max_tokens,
+                                                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                                                     repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k))
         return ChatCompletion.model_validate(data)
 
     def stream(self, *, model: str, messages: list[dict], temperature: float = 0.7, top_p: float = 0.9,
-               max_tokens: int = 256) -> AsyncChatStream:
+               max_tokens: int = 256, presence_penalty: Optional[float] = None,
+               frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+               logit_bias: Optional[dict] = None, seed: Optional[int] = None,
+               top_k: Optional[int] = None) -> AsyncChatStream:
         """Not a coroutine: returns the stream immediately (``async for`` / ``async with``)."""
-        return AsyncChatStream(self._c._stream(_chat_req(model, messages, temperature, top_p, max_tokens, True)))
+        return AsyncChatStream(self._c._stream(_chat_req(
+            model, messages, temperature, top_p, max_tokens, True,
+            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+            repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k)))
 
 
 class _AsyncEmbeddings:

@@ -18,6 +18,13 @@ class ChatCompletionRequest(BaseModel):
     top_p: float = 0.9
     max_tokens: int = 256
     stream: bool = False
+    # optional sampling controls: left out of the request body unless given
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    repetition_penalty: Optional[float] = None
+    logit_bias: Optional[dict[str, float]] = None
+    seed: Optional[int] = None
+    top_k: Optional[int] = None
 
 
 class EmbeddingRequest(BaseModel):

@@ -29,9 +29,10 @@ from typing import Optional
 from fastapi import Depends, FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, Response, StreamingResponse
 from prometheus_client import CONTENT_TYPE_LATEST, generate_latest
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, field_validator
 
 from vgate import metrics as M
+from vgate.backends.base import InvalidSamplingParams
 from vgate.batcher import RequestBatcher
 from vgate.config import VGateConfig, get_config, set_config
 from vgate.engine import VGateEngine
@@ -56,6 +57,43 @@ class ChatCompletionRequest(BaseModel):
     top_p: float = Field(0.9, gt=0.0, le=1.0)
     max_tokens: int = Field(256, ge=1)
     stream: bool = False
+    # optional sampling controls; None = not sent: such a request is served exactly as before
+    # (same cache key, same worker body, same engine step). Penalties act on the raw logits before
+    # temperature: repetition on prompt + output tokens, presence / frequency on output tokens.
+    presence_penalty: Optional[float] = Field(None, ge=-2.0, le=2.0)
+    frequency_penalty: Optional[float] = Field(None, ge=-2.0, le=2.0)
+    repetition_penalty: Optional[float] = Field(None, gt=0.0, le=10.0)
+    logit_bias: Optional[dict[str, float]] = None
+    seed: Optional[int] = Field(None, ge=0)
+    top_k: Optional[int] = Field(None, ge=1)
+
+    @field_validator("logit_bias")
+    @classmethod
+    def _check_logit_bias(cls, v):
+        if v is None:
+            return v
+        if len(v) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias holds more than {MAX_LOGIT_BIAS} entries")
+        for k, b in v.items():
+            if not (k.isascii() and k.isdigit()):
+                raise ValueError(f"logit_bias key {k!r} is not a decimal token id")
+            if not -100.0 <= b <= 100.0:  # (NaN fails too)
+                raise ValueError("logit_bias values must be in [-100, 100]")
+        return v
+
+    def extra(self) -> dict:
+        """The optional controls this request set, as keyword arguments of
+        ``backend.create_sampling_params`` (empty for a request without any)."""
+        out = {}
+        for name in EXTRA_FIELDS:
+            v = getattr(self, name)
+            if v is not None:
+                out[name] = v
+        return out
+
+
+MAX_LOGIT_BIAS = 300
+EXTRA_FIELDS = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias", "seed", "top_k")
 
 
 class EmbeddingRequest(BaseModel):
@@ -222,9 +260,13 @@ async def chat_completion_json(st: "AppState", request: "ChatCompletionRequest")
     """The non-streaming chat handler: (status, JSON body bytes, extra raw headers). Shared by the
     FastAPI route and :class:`ChatFastLane`; error bodies match FastAPI's HTTPException output."""
     prompt = messages_to_prompt(request.messages)
+    extra = request.extra()
+    kw = {"extra": extra} if extra else {}
     try:
         r = await st.batcher.submit(prompt, max_tokens=request.max_tokens, temperature=request.temperature,
-                                    top_p=request.top_p)
+                                    top_p=request.top_p, **kw)
+    except InvalidSamplingParams as e:  # e.g. a logit_bias id outside the model's vocabulary
+        return 400, _error_body(str(e)), []
     except NoHealthyWorkersError as e:
         app_logger.error("No healthy workers", extra={"extra_data": {"error": str(e)}})
         return 503, _error_body(str(e)), [(b"retry-after", b"5")]
@@ -556,7 +598,7 @@ async def _stream_chat(st: AppState, prompt: str, request: ChatCompletionRequest
             await sem.acquire()
             acquired = True
         sp = backend.create_sampling_params(temperature=request.temperature, top_p=request.top_p,
-                                            max_tokens=request.max_tokens)
+                                            max_tokens=request.max_tokens, **request.extra())
         async for piece in backend.stream_generate(prompt, sp):
             delta = piece.get("delta")
             n = piece.get("num_tokens", prev_n)

@@ -53,7 +53,10 @@ def _simulate_batch_compute(sampling_params: Any) -> None:
 class InferenceBackend(Protocol):
     def load_model(self, model_config: ModelConfig) -> None: ...
 
-    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int) -> Any: ...
+    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int, **extra) -> Any:
+        """``extra``: the optional sampling controls of a request (repetition_penalty,
+        presence_penalty, frequency_penalty, logit_bias, seed, top_k); passed only when one is set."""
+        ...
 
     def generate(self, prompts: List[str], sampling_params: Any) -> List[Dict[str, Any]]: ...
 
@@ -68,6 +71,11 @@ def _echo(prompt: str) -> str:
     return f"[dry-run] echo: {prompt[:80]}"
 
 
+class InvalidSamplingParams(ValueError):
+    """A request's sampling controls cannot be served by this backend (a logit_bias token outside
+    the vocabulary, processors under tensor parallelism): the API answers 400."""
+
+
 class DryRunBackend:
     """Placeholder generations without a GPU (CI, gateway/scaling benchmarks)."""
 
@@ -77,8 +85,8 @@ class DryRunBackend:
     def load_model(self, model_config: ModelConfig) -> None:
         pass
 
-    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int) -> Any:
-        return {"temperature": temperature, "top_p": top_p, "max_tokens": max_tokens}
+    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int, **extra) -> Any:
+        return {"temperature": temperature, "top_p": top_p, "max_tokens": max_tokens}  # extra: accepted, ignored
 
     @staticmethod
     def _result(prompt: str) -> Dict[str, Any]:

@@ -88,8 +88,8 @@ class NativeBackend:
             return
         self.engine.start()
 
-    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int) -> Any:
-        return {"temperature": temperature, "top_p": top_p, "max_tokens": max_tokens}
+    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int, **extra) -> Any:
+        return {"temperature": temperature, "top_p": top_p, "max_tokens": max_tokens, **extra}
 
     @staticmethod
     def _params(sp: Any):
@@ -100,7 +100,21 @@ class NativeBackend:
         return SamplingParams(temperature=float(sp.get("temperature", 0.7)), top_p=float(sp.get("top_p", 0.9)),
                               top_k=int(sp.get("top_k", -1)), max_tokens=int(sp.get("max_tokens", 256)),
                               seed=sp.get("seed"), stop=list(sp.get("stop") or []),
-                              ignore_eos=bool(sp.get("ignore_eos", False)))
+                              ignore_eos=bool(sp.get("ignore_eos", False)),
+                              repetition_penalty=float(sp.get("repetition_penalty", 1.0)),
+                              presence_penalty=float(sp.get("presence_penalty", 0.0)),
+                              frequency_penalty=float(sp.get("frequency_penalty", 0.0)),
+                              logit_bias=dict(sp.get("logit_bias") or {}))
+
+    def _add(self, rid: str, prompt: str, sampling_params: Any, cb, **kw):
+        """Queue a request; sampling controls the engine refuses (SamplingParams validation, a
+        logit_bias id outside the vocabulary, processors under tensor parallelism) are the
+        client's error, not an inference failure."""
+        from vgate.backends.base import InvalidSamplingParams
+        try:
+            return self.engine.add_request(rid, prompt, self._params(sampling_params), cb, **kw)
+        except ValueError as e:
+            raise InvalidSamplingParams(str(e)) from e
 
     @staticmethod
     def _result(seq) -> Dict[str, Any]:
@@ -127,7 +141,7 @@ class NativeBackend:
                 res = self._result(seq)
             done.push(fut, res)
 
-        self.engine.add_request(rid, prompt, self._params(sampling_params), cb)
+        self._add(rid, prompt, sampling_params, cb)
         try:
             return await fut
         except asyncio.CancelledError:
@@ -178,7 +192,7 @@ class NativeBackend:
             else:
                 loop.call_soon_threadsafe(q.put_nowait, ("end", seq.finish_reason, len(seq.output_ids)))
 
-        self.engine.add_request(rid, prompt, self._params(sampling_params), cb, stream=True)
+        self._add(rid, prompt, sampling_params, cb, stream=True)
         finished = False
         try:
             while True:

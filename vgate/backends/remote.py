@@ -36,6 +36,7 @@ try:  # imported with the module, not by the first request on the event loop (~0
 except ImportError:  # pragma: no cover - aiohttp is in requirements.txt
     _aiohttp = None
 
+from vgate.backends.base import InvalidSamplingParams
 from vgate.config import ModelConfig, WorkerConfig
 from vgate.logging_config import get_logger
 from vgate.metrics import WORKER_LATENCY, WORKER_REQUESTS, WORKER_RETRIES
@@ -199,8 +200,9 @@ class RemoteBackend:
     def load_model(self, model_config: ModelConfig) -> None:
         """No-op: workers own their models."""
 
-    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int) -> Any:
-        return {"temperature": temperature, "top_p": top_p, "max_tokens": max_tokens}
+    def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int, **extra) -> Any:
+        # the optional controls travel inside sampling_params (worker_api.WorkerSamplingParams)
+        return {"temperature": temperature, "top_p": top_p, "max_tokens": max_tokens, **extra}
 
     # ------------------------------------------------------------------ unary
     async def agenerate_batch(self, prompts: List[str], sampling_params: Any) -> List[Dict[str, Any]]:
@@ -245,6 +247,12 @@ class RemoteBackend:
                     WORKER_REQUESTS.labels(worker=ep, outcome="http_error").inc()
                     tried.add(ep)
                     continue
+                if status == 400:  # the worker's engine refused the sampling controls: the client's error
+                    try:
+                        detail = json.loads(raw).get("detail")
+                    except (ValueError, AttributeError):
+                        detail = None
+                    raise InvalidSamplingParams(str(detail or raw[:200].decode("utf-8", "replace")))
                 if status != 200:
                     self.registry.record_failure(ep)
                     WORKER_REQUESTS.labels(worker=ep, outcome="http_error").inc()

@@ -90,7 +90,8 @@ class RequestBatcher:
 
     # ------------------------------------------------------------------ submit
     async def submit(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
-                     top_p: Optional[float] = None, timeout: Optional[float] = None) -> Dict[str, Any]:
+                     top_p: Optional[float] = None, timeout: Optional[float] = None,
+                     extra: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         # no span objects at all while tracing is off (the serving default): this runs once per request
         cm = tracer.start_as_current_span("batcher.submit") if is_tracing_enabled() else _NO_SPAN
         with cm as span:
@@ -99,7 +100,9 @@ class RequestBatcher:
             temperature = cfg.inference.temperature if temperature is None else temperature
             top_p = cfg.inference.top_p if top_p is None else top_p
             span.set_attribute("prompt_length", len(prompt))
-            key = ResultCache.make_key(prompt, temperature, top_p, max_tokens)
+            # the optional sampling controls (penalties, logit_bias, seed, top_k): part of the key, so
+            # requests that differ in one of them are neither coalesced nor served each other's result
+            key = ResultCache.make_key(prompt, temperature, top_p, max_tokens, extra=extra or None)
             cached = self.cache.get_nowait(key)
             if cached:
                 span.set_attribute("cache_hit", True)
@@ -112,7 +115,8 @@ class RequestBatcher:
             if entry is None:
                 entry = _Inflight()
                 self._inflight[key] = entry
-                entry.task = asyncio.create_task(self._execute(entry, key, prompt, temperature, top_p, max_tokens))
+                entry.task = asyncio.create_task(self._execute(entry, key, prompt, temperature, top_p, max_tokens,
+                                                              extra or None))
                 entry.task.add_done_callback(functools.partial(self._retire, key))
             entry.waiters += 1
             span.set_attribute("deduplicated", coalesced)
@@ -141,7 +145,7 @@ class RequestBatcher:
             self._inflight.pop(key, None)
 
     async def _execute(self, entry: _Inflight, key: str, prompt: str, temperature: float, top_p: float,
-                       max_tokens: int) -> Dict[str, Any]:
+                       max_tokens: int, extra: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         queued_at = time.monotonic()
         self._waiting += 1
         PENDING_REQUESTS.set(self._waiting)
@@ -158,7 +162,10 @@ class RequestBatcher:
                 self.total_queue_samples += 1
                 INFLIGHT_INFERENCES.inc()
                 try:
-                    result = await self._run_inference(prompt, max_tokens, temperature, top_p)
+                    if extra:
+                        result = await self._run_inference(prompt, max_tokens, temperature, top_p, extra=extra)
+                    else:
+                        result = await self._run_inference(prompt, max_tokens, temperature, top_p)
                 finally:
                     INFLIGHT_INFERENCES.dec()
         finally:
@@ -170,7 +177,7 @@ class RequestBatcher:
 
     # --------------------------------------------------------------- inference
     async def _run_inference(self, prompt: str, max_tokens: int, temperature: float = 0.7,
-                             top_p: float = 0.9) -> Dict[str, Any]:
+                             top_p: float = 0.9, extra: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         backend = self.engine.backend
         t0 = time.perf_counter()
         try:
@@ -178,7 +185,9 @@ class RequestBatcher:
                 cm = tracer.start_as_current_span("batcher.inference") if is_tracing_enabled() else _NO_SPAN
                 with cm as span:
                     span.set_attribute("num_prompts", 1)
-                    sp = backend.create_sampling_params(temperature=temperature, top_p=top_p, max_tokens=max_tokens)
+                    # (**extra only when there is any: a backend may implement the three-argument form)
+                    sp = backend.create_sampling_params(temperature=temperature, top_p=top_p, max_tokens=max_tokens,
+                                                        **(extra or {}))
                     br = await backend.agenerate(prompt, sp)
                     result = self._shape(br, time.perf_counter() - t0)
                     span.set_attribute("total_tokens_generated", result["total_tokens"])
@@ -186,7 +195,7 @@ class RequestBatcher:
                 loop = asyncio.get_running_loop()
                 ctx = contextvars.copy_context()
                 result = await loop.run_in_executor(
-                    None, lambda: ctx.run(self._sync_inference_traced, prompt, max_tokens, temperature, top_p))
+                    None, lambda: ctx.run(self._sync_inference_traced, prompt, max_tokens, temperature, top_p, extra))
         except Exception as e:
             INFERENCE_ERRORS.labels(error_type=type(e).__name__).inc()
             logger.error("Inference error", extra={"extra_data": {"error": str(e), "error_type": type(e).__name__}})
@@ -209,17 +218,18 @@ class RequestBatcher:
         TOKENS_GENERATED.inc(result.get("total_tokens", 0))
         return result
 
-    def _sync_inference_traced(self, prompt, max_tokens, temperature, top_p):
+    def _sync_inference_traced(self, prompt, max_tokens, temperature, top_p, extra=None):
         with tracer.start_as_current_span("batcher.inference") as span:
             span.set_attribute("num_prompts", 1)
-            r = self._sync_inference(prompt, max_tokens, temperature, top_p)
+            r = self._sync_inference(prompt, max_tokens, temperature, top_p, extra)
             span.set_attribute("total_tokens_generated", r.get("total_tokens", 0))
             return r
 
     def _sync_inference(self, prompt: str, max_tokens: int, temperature: float = 0.7,
-                        top_p: float = 0.9) -> Dict[str, Any]:
+                        top_p: float = 0.9, extra: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         backend = self.engine.backend
-        sp = backend.create_sampling_params(temperature=temperature, top_p=top_p, max_tokens=max_tokens)
+        sp = backend.create_sampling_params(temperature=temperature, top_p=top_p, max_tokens=max_tokens,
+                                            **(extra or {}))
         t0 = time.perf_counter()
         br = backend.generate([prompt], sp)[0]
         return self._shape(br, time.perf_counter() - t0)

@@ -55,9 +55,15 @@ class ResultCache:
         self.evictions = 0
 
     @staticmethod
-    def make_key(prompt: str, temperature: float, top_p: float, max_tokens: int) -> str:
-        blob = json.dumps({"prompt": prompt, "temperature": temperature, "top_p": top_p,
-                           "max_tokens": max_tokens}, sort_keys=True)
+    def make_key(prompt: str, temperature: float, top_p: float, max_tokens: int,
+                 extra: Optional[dict[str, Any]] = None) -> str:
+        """``extra``: the optional sampling controls a request set (penalties, logit_bias, seed,
+        top_k). It joins the hashed JSON only when non-empty, so the keys of requests without them
+        are what they always were."""
+        fields = {"prompt": prompt, "temperature": temperature, "top_p": top_p, "max_tokens": max_tokens}
+        if extra:
+            fields["extra"] = extra
+        blob = json.dumps(fields, sort_keys=True)
         return hashlib.sha256(blob.encode("utf-8")).hexdigest()[:16]
 
     async def get(self, key: str) -> Optional[dict[str, Any]]:

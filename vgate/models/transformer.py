@@ -81,8 +81,11 @@ class ShardSpec:
 class DecoderModel:
     def __init__(self, arch: ModelArch, device: torch.device | str, tp: TPGroup | None = None,
                  quantization: str | None = None, seed: int = 0, weights_path: str | None = None,
-                 max_model_len: int = 4096):
+                 max_model_len: int = 4096, act_dtype: torch.dtype = torch.bfloat16):
         self.arch = arch
+        # activation dtype of the CPU reference path: bf16 mirrors the kernels' rounding; float32
+        # (EngineConfig.dtype, CPU only) keeps the forward exact against reference_logits
+        self.act_dtype = act_dtype
         self.device = torch.device(device)
         self.tp = tp or TPGroup()
         self.shard = ShardSpec(arch, self.tp)
@@ -272,13 +275,14 @@ class DecoderModel:
         T = sv.T
         D = a.head_dim
         dev = self.device
-        resid = ops.embedding(sv.ids, self.embed, vstart=sh.vocab0)
+        act = self.act_dtype
+        resid = ops.embedding(sv.ids, self.embed, vstart=sh.vocab0).to(act)
         if tp.size > 1:
             tp.all_reduce(resid)
         x = torch.empty_like(resid)
-        attn = torch.empty(T, sh.hq * D, dtype=torch.bfloat16, device=dev)
-        qkv = torch.empty(T, (sh.hq + 2 * sh.hkv) * D, dtype=torch.bfloat16, device=dev)
-        mlp = torch.empty(T, sh.inter, dtype=torch.bfloat16, device=dev)
+        attn = torch.empty(T, sh.hq * D, dtype=act, device=dev)
+        qkv = torch.empty(T, (sh.hq + 2 * sh.hkv) * D, dtype=act, device=dev)
+        mlp = torch.empty(T, sh.inter, dtype=act, device=dev)
         first = tp.is_first
         for li, L in enumerate(self.layers):
             kc, vc = kv_caches[li]

@@ -313,8 +313,11 @@ def linear(x: torch.Tensor, lin: Linear, out: torch.Tensor | None = None,
         ncols = qkv["hq"] * 128
     else:
         ncols = lin.N // 2 if silu else lin.N
+    # CPU reference path: fp32 activations in -> fp32 activations out (the engine's exact CPU mode,
+    # EngineConfig.dtype = "float32"); every other caller passes bf16 and gets the kernels' rounding
+    act = torch.float32 if not _gpu(x) and x.dtype == torch.float32 else torch.bfloat16
     if out is None:
-        out = torch.empty(M, ncols, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+        out = torch.empty(M, ncols, dtype=torch.float32 if out_f32 else act, device=x.device)
     if not _gpu(x):
         xx = x[row_idx.long()] if row_idx is not None else x
         if norm is not None:
@@ -322,16 +325,16 @@ def linear(x: torch.Tensor, lin: Linear, out: torch.Tensor | None = None,
         wd = lin.dense_weight()
         if silu:
             I = lin.N // 2
-            out.copy_(ref.silu_mul_linear_ref(xx, wd[:I], wd[I:]))
+            out.copy_(ref.silu_mul_linear_ref(xx, wd[:I], wd[I:], act=act))
         elif qkv is not None:
-            y = ref.linear_ref(xx, wd, lin.bias)
+            y = ref.linear_ref(xx, wd, lin.bias, act=act)
             ref.rope_kv_ref(y, qkv["positions"], qkv["slots"], qkv["cos_sin"], qkv["k_cache"], qkv["v_cache"],
                             qkv["hq"], qkv["hkv"], 128)
             out.copy_(y[:, :ncols])
             if attn is not None:
                 _attn_after(out, qkv, attn)
         else:
-            out.copy_(ref.linear_ref(xx, wd, lin.bias, residual, out_f32))
+            out.copy_(ref.linear_ref(xx, wd, lin.bias, residual, out_f32, act=act))
         return out
     C = native()
     epi = 3 if qkv is not None else (2 if silu else (1 if out_f32 else 0))
@@ -648,6 +651,18 @@ def sample(logits, temperature=None, top_p=None, top_k=None, seeds=None, offsets
     native().sample(logits, temperature, top_p, top_k, seeds, offsets, out, out_logprob, sample_workspace(logits.device),
                     fault_word(logits.device))
     return out
+
+
+def process_logits(logits, proc_view, prev_tokens=None):
+    """Repetition / presence / frequency penalties and logit_bias on the sampled rows before the
+    sampler (csrc/kernels/logits_proc.hip; ``proc_view``: vgate.runtime.logits_proc.ProcView).
+    GPU: in place, returns ``logits``. CPU: the sparse reference on a COPY, which is returned (the
+    caller's logits stay unprocessed)."""
+    pv = proc_view
+    if not _gpu(logits):
+        return ref.process_logits_sparse(logits.clone(), pv.row_off, pv.pend, pv.par, pv.entries, prev_tokens)
+    native().process_logits(logits, pv.row_off, pv.pend, pv.par, pv.entries, prev_tokens)
+    return logits
 
 
 def _plan_bucket(plan: dict, M: int):

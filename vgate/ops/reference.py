@@ -33,22 +33,24 @@ def embedding_ref(ids: torch.Tensor, table: torch.Tensor, vstart: int = 0) -> to
     return out * ok.unsqueeze(-1).to(out.dtype)
 
 
-def linear_ref(x: torch.Tensor, w: torch.Tensor, bias=None, residual=None, out_f32=False):
+def linear_ref(x: torch.Tensor, w: torch.Tensor, bias=None, residual=None, out_f32=False, act=torch.bfloat16):
+    """``act``: activation dtype the result is rounded to (bf16 mirrors the kernels' epilogues;
+    float32 = the CPU engine's exact mode, EngineConfig.dtype)."""
     y = x.float() @ w.float().t()
     if bias is not None:
         y = y + bias.float()
     if out_f32:
         return y
-    y = y.to(torch.bfloat16)
+    y = y.to(act)
     if residual is not None:
-        y = (y.float() + residual.float()).to(torch.bfloat16)
+        y = (y.float() + residual.float()).to(act)
     return y
 
 
-def silu_mul_linear_ref(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> torch.Tensor:
+def silu_mul_linear_ref(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, act=torch.bfloat16) -> torch.Tensor:
     g = x.float() @ w_gate.float().t()
     u = x.float() @ w_up.float().t()
-    return (torch.nn.functional.silu(g) * u).to(torch.bfloat16)
+    return (torch.nn.functional.silu(g) * u).to(act)
 
 
 def rope_cos_sin(max_pos: int, dim: int, theta: float, scaling: dict | None = None,
@@ -171,3 +173,82 @@ def awq_dequant_ref(qint: torch.Tensor, scales: torch.Tensor, zeros: torch.Tenso
     s = scales.float().t().repeat_interleave(group, dim=1)  # [N, K]
     z = zeros.float().t().repeat_interleave(group, dim=1)
     return ((qint.float() - z) * s).to(torch.bfloat16)
+
+
+# ----------------------------------------------------------------------------- logits processors
+def _penalise(x, cnt, in_prompt, bias, par):
+    """The sparse path's arithmetic on gathered fp32 values: par = {rep, inv_rep, pres, freq} as fp32
+    scalars (inv_rep comes from the host, as the kernel reads it), every step one rounded operation."""
+    rep, inv_rep, pres, freq = par[0], par[1], par[2], par[3]
+    if float(rep) != 1.0:
+        seen = in_prompt | (cnt > 0)
+        x = torch.where(seen, torch.where(x > 0, x * inv_rep, x * rep), x)
+    x = x - freq * cnt.to(torch.float32)
+    x = torch.where(cnt > 0, x - pres, x)
+    return x + bias
+
+
+def process_logits_ref(logits: torch.Tensor, prompt_ids, output_ids, params) -> torch.Tensor:
+    """Dense oracle of the logits processors for ONE row ``logits`` [V] (fp32): counts by bincount
+    over the whole vocabulary, then the penalty / bias steps on every element. ``output_ids`` includes
+    every token generated so far (the in-flight one too). Returns a new tensor."""
+    x = logits.detach().float().cpu().clone()
+    V = x.numel()
+    out = torch.as_tensor(list(output_ids), dtype=torch.int64)
+    prm = torch.as_tensor(list(prompt_ids), dtype=torch.int64)
+    cnt = torch.bincount(out[(out >= 0) & (out < V)], minlength=V)
+    in_prompt = torch.bincount(prm[(prm >= 0) & (prm < V)], minlength=V) > 0
+    bias = torch.zeros(V, dtype=torch.float32)
+    for t, b in params.logit_bias.items():
+        if 0 <= int(t) < V:
+            bias[int(t)] = float(b)
+    f32 = torch.float32
+    rep = torch.tensor(params.repetition_penalty, dtype=f32)
+    if float(rep) != 1.0:  # 1. repetition: prompt and output tokens
+        inv_rep = torch.tensor(1.0, dtype=f32) / rep
+        x = torch.where(in_prompt | (cnt > 0), torch.where(x > 0, x * inv_rep, x * rep), x)
+    x = x - torch.tensor(params.frequency_penalty, dtype=f32) * cnt.to(f32)  # 2. frequency: product, then difference
+    x = torch.where(cnt > 0, x - torch.tensor(params.presence_penalty, dtype=f32), x)  # 3. presence
+    return x + bias  # 4. bias
+
+
+def process_logits_sparse(logits: torch.Tensor, row_off, pend, par, entries, prev=None) -> torch.Tensor:
+    """The logits kernel's algorithm on the host, in place on ``logits`` [S, V] fp32 (CPU): row r's
+    unique-token entries {tok, cnt (bit 31 = in prompt), bias bits, pad} are
+    entries[row_off[r]: row_off[r + 1]], par[r] = {rep, inv_rep, pres, freq}, pend[r] = 0 or
+    -(slot + 1) of the sequence's in-flight token in ``prev``."""
+    S, V = logits.shape
+    row_off = torch.as_tensor(row_off).tolist()
+    pend = torch.as_tensor(pend).tolist()
+    par = torch.as_tensor(par).reshape(-1, 4)
+    entries = torch.as_tensor(entries).reshape(-1, 4)
+    for r in range(S):
+        a, b = max(row_off[r], 0), min(row_off[r + 1], entries.shape[0])
+        p = -1
+        if pend[r] < 0 and prev is not None:
+            slot = min(max(-(pend[r] + 1), 0), prev.numel() - 1)
+            p = int(prev[slot])
+            if not 0 <= p < V:
+                p = -1
+        if b <= a and p < 0:
+            continue
+        e = entries[a:b] if b > a else entries[:0]
+        tok = e[:, 0].to(torch.int64)
+        word = e[:, 1].to(torch.int64)
+        cnt = word & 0x7FFFFFFF
+        in_prompt = word < 0
+        bias = e[:, 2].contiguous().view(torch.float32)
+        ok = (tok >= 0) & (tok < V)
+        tok, cnt, in_prompt, bias = tok[ok], cnt[ok], in_prompt[ok], bias[ok]
+        if p >= 0:
+            hit = tok == p
+            if bool(hit.any()):
+                cnt = cnt + hit.to(cnt.dtype)
+            else:
+                tok = torch.cat([tok, torch.tensor([p])])
+                cnt = torch.cat([cnt, torch.tensor([1])])
+                in_prompt = torch.cat([in_prompt, torch.tensor([False])])
+                bias = torch.cat([bias, torch.zeros(1)])
+        row = logits[r]
+        row[tok] = _penalise(row[tok], cnt, in_prompt, bias, par[r].float())
+    return logits

@@ -30,6 +30,7 @@ from vgate.models.config import resolve_arch
 from vgate.models.transformer import DecoderModel
 from vgate.parallel.comm import TPGroup, init_tp
 from vgate.runtime.kv_cache import BLOCK_SIZE, KVCacheManager, allocate_kv_tensors
+from vgate.runtime.logits_proc import SeqProcState, check_request
 from vgate.runtime.model_runner import ModelRunner
 from vgate.runtime.sampling_params import SamplingParams
 from vgate.runtime.scheduler import Scheduler
@@ -55,6 +56,10 @@ class EngineConfig:
     weights_path: str | None = None
     tokenizer: str | None = None
     quantization: str | None = None
+    # activations and KV cache: "bfloat16" (what the gfx950 kernels compute in; the CPU reference path
+    # mirrors their rounding). "float32" on a CPU device keeps the reference path's activations and KV
+    # cache in fp32, so the engine reproduces the dense fp32 forward (model.reference_logits) token for
+    # token: for checking engine logic exactly. A GPU engine computes in bf16 whatever this says.
     dtype: str = "bfloat16"
     device: str = "auto"
     tensor_parallel_size: int = 1
@@ -162,8 +167,10 @@ class LLMEngine:
             weights = os.path.expanduser(cfg.model)
         self.arch = resolve_arch(cfg.model, cfg.arch_overrides)
         t0 = time.perf_counter()
+        self.act_dtype = torch.float32 if cfg.dtype in ("float32", "fp32") and self.device.type == "cpu" \
+            else torch.bfloat16
         self.model = DecoderModel(self.arch, self.device, self.tp, cfg.quantization, cfg.seed, weights,
-                                  cfg.max_model_len)
+                                  cfg.max_model_len, act_dtype=self.act_dtype)
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         self.load_seconds = time.perf_counter() - t0
@@ -172,7 +179,8 @@ class LLMEngine:
         if self.tp.custom_ar is not None and cfg.tp_collective_self_check and not self.tp.simulated:
             self._collective_self_check()
         self.kv_caches = allocate_kv_tensors(self.arch.num_layers, self.num_blocks, self.model.num_kv_heads_local,
-                                             self.arch.head_dim, self.device, block_size=cfg.block_size)
+                                             self.arch.head_dim, self.device, dtype=self.act_dtype,
+                                             block_size=cfg.block_size)
         self.kvm = KVCacheManager(self.num_blocks, cfg.block_size, cfg.enable_prefix_caching)
         self.scheduler = Scheduler(self.kvm, cfg.max_num_seqs, cfg.max_num_batched_tokens, cfg.max_model_len)
         part = cfg.part_size or 512
@@ -329,6 +337,9 @@ class LLMEngine:
             prompt_ids = prompt_ids[-(self.cfg.max_model_len - 1):]
         seq = Sequence(request_id=request_id, prompt_ids=list(prompt_ids), params=params, callback=callback,
                        stream=stream)
+        if params.has_processors:
+            check_request(params, self.arch.vocab_size, self.tp.size)
+            seq.proc = SeqProcState(seq.prompt_ids, params.logit_bias)
         seq.seed = params.seed if params.seed is not None else \
             (self.cfg.seed * 1000003 + zlib.crc32(request_id.encode())) & 0x7FFFFFFFFFFFFFFF
         if stream:
@@ -418,7 +429,7 @@ class LLMEngine:
         while self._running:
             if self.ring is not None:
                 self.ring.heartbeat()
-            if self.runner.pending_captures and self._idle():
+            if self.runner.captures_pending and self._idle():
                 # buckets first seen under load ran eagerly; capture them once the engine has
                 # stayed idle for a moment (not in the microseconds between two requests of a
                 # running load), one bucket at a time, re-checking for new work in between
@@ -431,9 +442,10 @@ class LLMEngine:
                         log.exception("deferred hipGraph capture failed")
                         self.runner.defer_capture_failed = True
                         self.runner.pending_captures.clear()
+                        self.runner.proc_pending.clear()
             with self._cv:
                 t_idle0 = None
-                while self._running and self._idle() and not self.runner.pending_captures:
+                while self._running and self._idle() and not self.runner.captures_pending:
                     if self.ring is not None:  # an idle TP group must not look dead to its followers
                         self.ring.heartbeat()
                     t_idle = self._idle_t = time.perf_counter()
@@ -631,6 +643,8 @@ class LLMEngine:
                     continue
                 seq.output_ids.append(tok)
                 nout = len(seq.output_ids)
+            if seq.proc is not None:  # the token is known to the host now: count it (O(1))
+                seq.proc.add_output(tok)
             self.kvm.register_computed(seq)
             st.tokens_generated += 1
             if seq.first_token_time is None:
@@ -905,6 +919,7 @@ class LLMEngine:
             "graph_misses_eager": self.runner.graph_misses,
             "pending_captures": len(self.runner.pending_captures),
             "graph_captures": self.runner.captures,
+            "proc_steps": self.runner.proc_steps, "proc_graphs_captured": len(self.runner.proc_graphs),
             "graph_hit_ratio": round(self.runner.graph_hits / max(1, self.runner.graph_hits + self.runner.graph_misses), 4),
             "max_gpu_step_ms": round(self.runner.max_gpu_ms, 3),
             "max_gpu_step_bucket": list(self.runner.max_gpu_bucket),

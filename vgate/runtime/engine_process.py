@@ -76,6 +76,7 @@ def _core_main(cfg, conn, snap_period: float = 0.25) -> None:
     def snap() -> dict:
         s = eng.snapshot()
         s["healthy"] = bool(eng.healthy)
+        s["vocab_size"] = int(eng.arch.vocab_size)
         s["has_work"] = bool(eng.has_unfinished())
         s["last_step_age_s"] = time.monotonic() - eng.last_step_wall
         return s
@@ -108,7 +109,10 @@ def _core_main(cfg, conn, snap_period: float = 0.25) -> None:
             op = msg[0]
             if op == "add":
                 _, rid, prompt, ids, params, stream = msg
-                eng.add_request(rid, prompt, params, make_cb(rid), stream=stream, prompt_ids=ids)
+                try:
+                    eng.add_request(rid, prompt, params, make_cb(rid), stream=stream, prompt_ids=ids)
+                except ValueError as e:  # refused at admission: that request fails, the core goes on
+                    send(("rej", rid, f"{type(e).__name__}: {e}"))
             elif op == "abort":
                 eng.abort(msg[1])
             elif op == "call":
@@ -213,6 +217,10 @@ class EngineProcessClient:
                                                                            f["finish_time"])
                         if cb is not None:
                             cb(kind, sv, err)
+                elif op == "rej":
+                    ent = self._seqs.pop(msg[1], None)
+                    if ent is not None and ent[1] is not None:
+                        ent[1]("error", ent[0], msg[2])
                 elif op == "snap":
                     self._snap, self._snap_t = msg[1], time.monotonic()
                 elif op == "ret":
@@ -251,8 +259,12 @@ class EngineProcessClient:
 
     def add_request(self, request_id: str, prompt: str | None = None, params=None, callback=None,
                     stream: bool = False, prompt_ids: list[int] | None = None) -> SeqView:
+        from vgate.runtime.logits_proc import check_request
         from vgate.runtime.sampling_params import SamplingParams
 
+        if params is not None and "vocab_size" in self._snap:
+            # refused here as LLMEngine.add_request refuses it (ValueError to the caller)
+            check_request(params, self._snap["vocab_size"], 1)
         sv = SeqView(request_id)
         self._seqs[request_id] = (sv, callback)
         if not self._running:

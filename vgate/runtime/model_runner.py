@@ -14,6 +14,13 @@ yet is passed as ``-(slot + 1)`` and resolved on the device from the previous
 step's sampler output (``out_tokens``), so step t+1 is queued behind step t while
 the host post-processes t: the GPU never idles between steps. Host metadata and
 host-side sample buffers are double-buffered for that overlap.
+
+Logits processors (penalties, logit_bias): a step in which at least one sampling row belongs to a
+request with processors is a *processor step*. It uploads a second buffer (ProcMeta: the rows'
+unique-token entries) and runs one more kernel between the forward and the sampler, which also
+resolves the row's in-flight token on the device. Processor steps replay their own graphs
+(``proc_graphs``, captured on first use or at idle, never at warm-up); ``graphs`` and every plain
+step are exactly what they are without the feature.
 """
 from __future__ import annotations
 
@@ -26,6 +33,7 @@ import numpy as np
 import torch
 
 from vgate import ops
+from vgate.runtime.logits_proc import ProcMeta
 from vgate.runtime.scheduler import ScheduledBatch
 from vgate.runtime.step_meta import StepMeta
 from vgate.utils.profiling import range_
@@ -78,6 +86,12 @@ class ModelRunner:
         self.tile_lead = ops.flash_lead(sh.hq, sh.hkv) if sh is not None else 32
         self.graph_ok = lambda T, S: True  # per-bucket veto (TP groups without capturable collectives)
         self.graphs: dict[tuple[int, int], tuple] = {}
+        # processor steps: their own graph table (forward + logits kernel + sampler) and step buffer
+        self.proc_graphs: dict[tuple[int, int], tuple] = {}
+        self.proc_pending: dict[tuple[int, int], int] = {}
+        self.procmeta: ProcMeta | None = None  # allocated on the first processor step, never regrown
+        self.proc_steps = 0
+        self.max_model_len = max_model_len
         self.pool = None
         # rounded up to 4 ids: the sampled-id download moves 16-B pieces (ops.host_device_copy)
         self.out_tokens = torch.zeros((self.max_seqs + 3) // 4 * 4, dtype=torch.int32, device=self.device)
@@ -230,9 +244,40 @@ class ModelRunner:
         tseq[:ntile] = ts[o]
         tq0[:ntile] = tq[o]
 
+    # ------------------------------------------------------- logits processors
+    def _fill_proc(self, batch: ScheduledBatch, samples: list[bool], S: int, k: int,
+                   pending_slots: dict | None = None) -> bool:
+        """Pack and upload the processor buffer of a step (host buffer ``k``). A row gets entries only
+        when its request has processors AND this step consumes its sample; its in-flight token (if
+        any) travels as -(slot + 1), like the step's token ids. False: a plain step, nothing done."""
+        rows = None
+        for s, ((seq, _), smp) in enumerate(zip(batch.items, samples)):
+            st = seq.proc
+            if st is None or not smp:
+                continue
+            if rows is None:
+                rows = [None] * len(batch.items)
+            pend = -(pending_slots[seq.seq_id] + 1) if pending_slots and seq.pending else 0
+            rows[s] = (st, seq.params, pend)
+        if rows is None:
+            return False
+        pm = self._procmeta()
+        if pm.fill(k, rows, S) == 0:
+            return False
+        pm.upload(k)
+        self.proc_steps += 1
+        return True
+
+    def _procmeta(self) -> ProcMeta:
+        if self.procmeta is None:
+            self.procmeta = ProcMeta(self.max_seqs, self.model.arch.vocab_size, self.max_model_len, self.device)
+        return self.procmeta
+
     # ----------------------------------------------------------------- forward
-    def _forward_sample(self, view):
+    def _forward_sample(self, view, proc=None):
         logits = self.model.forward(view, self.kv, self.part_size)
+        if proc is not None:  # processor step: penalties / bias in place on the sampled rows
+            ops.process_logits(logits, proc, view.prev_tokens)
         ops.sample(logits, view.temperature, view.top_p, view.top_k, view.seeds, view.offsets,
                    out=self.out_tokens[: view.S])
         if self.gpu:  # last node of the step graph: sampled ids (+ fault / collective words) -> pinned ring slot
@@ -240,29 +285,31 @@ class ModelRunner:
                                      fault=self.fault)
         return logits
 
-    def _capture(self, T: int, S: int):
-        with range_(f"vgate.capture T={T} S={S}"):
-            return self._capture_impl(T, S)
+    def _capture(self, T: int, S: int, proc: bool = False):
+        with range_(f"vgate.capture T={T} S={S}" + (" proc" if proc else "")):
+            return self._capture_impl(T, S, proc)
 
-    def _capture_impl(self, T: int, S: int):
+    def _capture_impl(self, T: int, S: int, proc: bool = False):
         t0 = time.perf_counter()
         view = self.meta.view(T, S)
+        pv = self._procmeta().view(S) if proc else None
         # warm-up (eager) on the capture stream, then capture
         s = self.stream
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._forward_sample(view)
+            self._forward_sample(view, pv)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         if self.pool is None:
             self.pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self.pool, stream=s):
-            logits = self._forward_sample(view)
+            logits = self._forward_sample(view, pv)
         # the graph's static residual + logits tensors (the TP consistency guard reads them), owned by
         # the graph object: dropping a graph drops them with it (references kept beside a deleted
         # graph would pin blocks of its private pool, which the next capture into that pool asserts on)
         g.vg_out = (self.model.last_resid, logits)
+        g.vg_proc = proc
         torch.cuda.synchronize()
         self.captures += 1
         self.capture_seconds += time.perf_counter() - t0
@@ -305,14 +352,16 @@ class ModelRunner:
         if timed:
             self.started[k].record()
         self.meta.upload(ns)
+        proc = self._fill_proc(batch, samples, S, k, pending_slots)
+        table, pending = (self.proc_graphs, self.proc_pending) if proc else (self.graphs, self.pending_captures)
         self._uncollected[k] = True
         graphs = self.use_graphs and self.graph_ok(T, S)
-        g = self.graphs.get((T, S)) if graphs else None
+        g = table.get((T, S)) if graphs else None
         if g is None and graphs and not self.defer_capture:
             # the capture's eager warm-up samples into out_tokens, which this step may
             # still have to read (ids < 0): keep the previous step's samples aside
             saved = self.out_tokens.clone()
-            g = self.graphs[(T, S)] = self._capture(T, S)
+            g = table[(T, S)] = self._capture(T, S, proc)
             self.out_tokens.copy_(saved)
         eager = g is None
         if g is not None:
@@ -327,10 +376,10 @@ class ModelRunner:
                 # a capture (eager warm-up + record, ~0.1-0.5 s) would stall every in-flight
                 # request behind this step
                 self.graph_misses += 1
-                self.pending_captures[(T, S)] = self.pending_captures.get((T, S), 0) + 1
+                pending[(T, S)] = pending.get((T, S), 0) + 1
             view = self.meta.view(T, S)
             view.num_tokens, view.num_seqs = nt, ns
-            lg = self._forward_sample(view)
+            lg = self._forward_sample(view, self.procmeta.view(S) if proc else None)
             if check:
                 self.check_words = self._words(self.model.last_resid, lg, nt, ns)
         self.dones[k].record()
@@ -433,19 +482,22 @@ class ModelRunner:
         self.meta.upload(ns)
         view = self.meta.view(nt, ns)
         view.num_tokens, view.num_seqs = nt, ns
-        logits = self._cpu_sample(view, batch)
+        proc = self._fill_proc(batch, samples, ns, 0)
+        logits = self._cpu_sample(view, batch, self.procmeta.view(ns) if proc else None)
         if check:
             self.check_words = self._words(self.model.last_resid, logits, nt, ns)
         return self.out_tokens[:ns].tolist(), samples
 
-    def _cpu_sample(self, view, batch):
+    def _cpu_sample(self, view, batch, proc=None):
         logits = self.model.forward(view, self.kv, self.part_size)
+        # the sampler reads a processed copy; the raw logits go back to the caller (TP checksum)
+        sampled = ops.process_logits(logits, proc, None) if proc is not None else logits
         gens = []
         for seq, _ in batch.items:
             g = torch.Generator()
             g.manual_seed((seq.seed * 1000003 + len(seq.output_ids)) & 0x7FFFFFFFFFFFFFFF)
             gens.append(g)
-        self.out_tokens[: view.S] = ops.ref.sample_ref(logits, view.temperature, view.top_p, view.top_k, gens)
+        self.out_tokens[: view.S] = ops.ref.sample_ref(sampled, view.temperature, view.top_p, view.top_k, gens)
         return logits
 
     def warmup(self, token_buckets: list[int] | None = None, seq_buckets: list[int] | None = None) -> float:
@@ -528,21 +580,35 @@ class ModelRunner:
             if check:
                 self.check_words = self._words(self.model.last_resid, lg, nt, ns)
 
+    @property
+    def captures_pending(self) -> bool:
+        """Buckets (plain or processor steps) that ran eagerly and wait for an idle-time capture."""
+        return bool(self.pending_captures or self.proc_pending)
+
+    @torch.inference_mode()
     def capture_pending(self, max_graphs: int = 64) -> int:
         """Capture the buckets that ran eagerly since the last call (most frequent first).
-        Call only with no step in flight: captures reuse the step-metadata buffers."""
-        if not self.use_graphs or not self.pending_captures:
+        Call only with no step in flight: captures reuse the step-metadata buffers. (Inference mode
+        like launch(): a capture begun outside it cannot reset the graph-safe RNG state that an
+        on-miss capture inside launch() created as an inference tensor.)"""
+        if not self.use_graphs or not (self.pending_captures or self.proc_pending):
             return 0
-        keys = sorted(self.pending_captures, key=lambda k: -self.pending_captures[k])[:max_graphs]
+        keys = [(c, key, False) for key, c in self.pending_captures.items()]
+        keys += [(c, key, True) for key, c in self.proc_pending.items()]
+        keys = sorted(keys, key=lambda e: -e[0])[:max_graphs]
         t0 = time.perf_counter()
         n = 0
-        for T, S in keys:
-            if (T, S) not in self.graphs:
+        for _, (T, S), proc in keys:
+            table, pending = (self.proc_graphs, self.proc_pending) if proc else (self.graphs, self.pending_captures)
+            if (T, S) not in table:
                 self._fill_padding(T, S)
                 self.meta.upload(0)
-                self.graphs[(T, S)] = self._capture(T, S)
+                if proc:  # all-empty processor header: the warm-up run's logits blocks exit at once
+                    self.procmeta.fill_empty(self._k, S)
+                    self.procmeta.upload(self._k)
+                table[(T, S)] = self._capture(T, S, proc)
                 n += 1
-            del self.pending_captures[(T, S)]  # removed last: present means "capture still to come"
+            del pending[(T, S)]  # removed last: present means "capture still to come"
         log.info("captured %d deferred hipGraph bucket(s) in %.2fs", n, time.perf_counter() - t0)
         return n
 

@@ -1,6 +1,7 @@
 """Per-request sampling parameters for the native engine."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 
 
@@ -15,6 +16,12 @@ class SamplingParams:
     stop: list[str] = field(default_factory=list)
     ignore_eos: bool = False
     min_tokens: int = 0
+    # logits processors (csrc/kernels/logits_proc.hip), applied to the raw logits before temperature:
+    # repetition covers prompt + output tokens, presence / frequency the output tokens only
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: dict[int, float] = field(default_factory=dict)
 
     def __post_init__(self):
         if self.temperature < 0:
@@ -25,7 +32,29 @@ class SamplingParams:
             raise ValueError("max_tokens must be >= 1")
         if self.top_k == 0:
             self.top_k = -1
+        if not (math.isfinite(self.repetition_penalty) and self.repetition_penalty > 0):
+            raise ValueError("repetition_penalty must be finite and > 0")
+        if not (math.isfinite(self.presence_penalty) and math.isfinite(self.frequency_penalty)):
+            raise ValueError("presence_penalty and frequency_penalty must be finite")
+        if self.logit_bias:
+            bias = {}
+            for k, v in self.logit_bias.items():
+                k, v = int(k), float(v)
+                if k < 0:
+                    raise ValueError("logit_bias keys must be token ids >= 0")
+                if not math.isfinite(v):
+                    raise ValueError("logit_bias values must be finite")
+                bias[k] = v
+            self.logit_bias = bias
+        else:
+            self.logit_bias = {}
 
     @property
     def greedy(self) -> bool:
         return self.temperature <= 1e-5
+
+    @property
+    def has_processors(self) -> bool:
+        """Any logits processor differs from its default (the step then runs the logits kernel)."""
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+                or bool(self.logit_bias))

@@ -51,6 +51,8 @@ class Sequence:
     # device, not yet seen by the host) and the sample slot of the newest one
     pending: collections.deque = field(default_factory=collections.deque)
     pending_slot: int = -1
+    # logits processors: unique-token entries (vgate.runtime.logits_proc.SeqProcState), None = plain
+    proc: object = None
 
     @property
     def all_ids(self) -> list[int]:

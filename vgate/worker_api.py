@@ -3,7 +3,9 @@
 ``POST /internal/generate`` keeps the reference wire contract
 (``{prompts: [str] (>=1), sampling_params: {temperature, top_p, max_tokens}}`` ->
 ``{results: [backend result dicts]}``; 503 before the engine is bound; 500
-``Inference failed: <Type>``). Async backends are awaited concurrently on the
+``Inference failed: <Type>``). ``sampling_params`` may also carry the optional sampling controls
+(repetition / presence / frequency penalty, logit_bias, seed, top_k; absent unless the client sent
+them); controls the worker's engine refuses (a logit_bias id outside the vocabulary) answer 400. Async backends are awaited concurrently on the
 loop (each prompt is its own engine request, so they batch continuously);
 sync backends run in the executor, serialised by a lock if not concurrency-safe.
 
@@ -28,6 +30,7 @@ from fastapi import APIRouter, HTTPException, Request
 from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field
 
+from vgate.backends.base import InvalidSamplingParams
 from vgate.logging_config import get_logger
 from vgate.metrics import INFERENCE_ERRORS
 from vgate.tracing import attach_traceparent, get_tracer
@@ -97,6 +100,18 @@ class WorkerSamplingParams(BaseModel):
     temperature: float = 0.7
     top_p: float = 0.9
     max_tokens: int = 256
+    # optional sampling controls (validated by the gateway's ChatCompletionRequest); None = not sent
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    logit_bias: Optional[dict[int, float]] = None
+    seed: Optional[int] = None
+    top_k: Optional[int] = None
+
+    def extra(self) -> dict:
+        """The controls that were sent, as keyword arguments of create_sampling_params."""
+        return {k: v for k, v in self.model_dump(exclude={"temperature", "top_p", "max_tokens"}).items()
+                if v is not None}
 
 
 class GenerateRequest(BaseModel):
@@ -140,7 +155,7 @@ async def _generate(body: GenerateRequest, request: Request):
             span.set_attribute("num_prompts", len(body.prompts))
             sp_in = body.sampling_params
             sp = backend.create_sampling_params(temperature=sp_in.temperature, top_p=sp_in.top_p,
-                                                max_tokens=sp_in.max_tokens)
+                                                max_tokens=sp_in.max_tokens, **sp_in.extra())
             try:
                 if hasattr(backend, "agenerate"):
                     results = list(await asyncio.gather(*(backend.agenerate(p, sp) for p in body.prompts)))
@@ -151,6 +166,8 @@ async def _generate(body: GenerateRequest, request: Request):
                             results = await loop.run_in_executor(None, backend.generate, body.prompts, sp)
                     else:
                         results = await loop.run_in_executor(None, backend.generate, body.prompts, sp)
+            except InvalidSamplingParams as e:
+                raise HTTPException(status_code=400, detail=str(e))
             except Exception as e:  # noqa: BLE001
                 INFERENCE_ERRORS.labels(error_type=type(e).__name__).inc()
                 logger.error("Worker inference failed", extra={"extra_data": {
@@ -168,7 +185,8 @@ async def internal_generate_stream(body: StreamRequest, request: Request):
     if not getattr(backend, "supports_streaming", False):
         raise HTTPException(status_code=501, detail="worker backend cannot stream")
     sp_in = body.sampling_params
-    sp = backend.create_sampling_params(temperature=sp_in.temperature, top_p=sp_in.top_p, max_tokens=sp_in.max_tokens)
+    sp = backend.create_sampling_params(temperature=sp_in.temperature, top_p=sp_in.top_p, max_tokens=sp_in.max_tokens,
+                                        **sp_in.extra())
 
     # the stream counts from ACCEPTANCE (here, before the response object exists) to its last byte:
     # a drain that starts between this point and the server's first iteration of the body still
