@@ -270,3 +270,23 @@ def active_k(p: Problem, k0: int = 0) -> int:
     """A column k >= k0 in which some row of x is non-zero (so a change of W[:, k] shows)."""
     nz = (p.x.double().abs().sum(0) > 0).nonzero().flatten()
     return int(nz[nz >= k0][0])
+
+
+def launches(fn, device: str = "cuda") -> list[tuple]:
+    """The launch-timeline entries (name, offset, blocks) of the launches ``fn`` makes (GPU tests)."""
+    import pytest
+
+    from vgate import ops
+    C = ops.native()
+    buf = torch.zeros(1 << 17, dtype=torch.int64, device=device)
+    C.timeline_start(buf)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    except RuntimeError as e:  # a GPU fault: nothing more may start on this device in this session
+        if "hip" in str(e).lower() or "illegal" in str(e).lower():
+            pytest.exit(f"GPU fault, session ended: {e}", returncode=3)
+        raise
+    finally:
+        C.timeline_stop()
+    return C.timeline_entries()

@@ -112,23 +112,6 @@ class Guarded:
                                  f"{rc[:6].tolist()} of {tuple(self.big.shape)} (view starts at row {X.GUARD})")
 
 
-def launches(fn) -> list[tuple]:
-    """The timeline entries (name, offset, blocks) of the launches ``fn`` makes."""
-    C = ops.native()
-    buf = torch.zeros(1 << 17, dtype=torch.int64, device=DEV)
-    C.timeline_start(buf)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    except RuntimeError as e:  # a GPU fault: nothing more may start on this device in this session
-        if "hip" in str(e).lower() or "illegal" in str(e).lower():
-            pytest.exit(f"GPU fault, session ended: {e}", returncode=3)
-        raise
-    finally:
-        C.timeline_stop()
-    return C.timeline_entries()
-
-
 def assert_exact(got: torch.Tensor, want: torch.Tensor, what: str) -> None:
     """Every element equal by value (0 * negative is -0)."""
     got = got.detach().cpu().double()
@@ -212,14 +195,14 @@ def launch(p: X.Problem, lin: ops.Linear, mode: str, knobs: dict, twice: bool = 
                   k_cache=kc, v_cache=vc, hq=m["hq"], hkv=m["hkv"])
     if p.awq is not None:
         kw.update(awq_scales=lin.scales, awq_zeros=lin.zeros, group=lin.group)
-        if getattr(lin, "szp", None) is not None:
+        if lin.szp is not None:
             kw["awq_szp"] = lin.szp
 
     def go():
         C.gemm(xg.view, lin.wp, N, K, og.view, epi, **kw)
 
     fault0 = int(ops.fault_word(DEV)[0])
-    ents = launches(go)
+    ents = X.launches(go)
     r["names"], r["blocks"] = [e[0] for e in ents], [e[2] for e in ents]
     what = f"{mode} {knobs} {r['names']}"
     for name, b in bufs.items():

@@ -122,6 +122,19 @@ def test_tune_prefill_without_gpu_is_a_no_op():
     assert lin.prefill_plan == {}
 
 
+def test_handoff_caches_are_the_ones_the_package_exports():
+    """tests/conftest.py checks the ticket words after every GPU test through ``ops._WS`` and
+    ``ops._TICKETS``: they must be the dicts that hold the live tensors, keyed by device."""
+    from vgate.ops import buffers
+    assert ops._WS is buffers._WS and ops._TICKETS is buffers._TICKETS
+    assert ops.workspace("cpu") is ops._WS["cpu"] and ops.attn_tickets("cpu") is ops._TICKETS["cpu"]
+    assert ops.workspace("cpu").numel() > buffers.WS_TICKET_WORDS == 65536
+    ops.workspace("cpu")[:4] = 1
+    ops.fault_word("cpu")[0] = 4
+    ops.reset_handoffs("cpu")
+    assert int(ops.workspace("cpu")[:4].sum()) == 0 and int(ops.fault_word("cpu")[0]) == 0
+
+
 def test_host_device_copy_cpu_fallback():
     """Without a GPU tensor the helper is a plain prefix copy (the CPU engine's path)."""
     src = torch.arange(64, dtype=torch.int32)

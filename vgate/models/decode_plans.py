@@ -9,13 +9,15 @@ their current plan (benchmarks/decode_sweep.py for TP = 1 models, benchmarks/tp_
 
 Key: (N, K, layout, weight kind) of the packed weight; layout "qkv" / "silu" / "plain".
 Value: (waves, K slices, column tiles per block) of the tile-per-block kernels, ("kx", waves, K
-slices, tiles code) for the register-stationary kernel (path 4; 0 = its own grid rule), or
+slices, tiles code) for the register-stationary kernel (PATH_KX; 0 = its own grid rule), or
 ("sk", waves, blocks per CU, k-steps per register group) for the stream-K kernel
 (csrc/kernels/gemm_streamk.hip: one equal share of the weight stream per CU), which wins on the
 large matrices where the tile count leaves CUs uneven (benchmarks/probes/sk_probe.py,
 profiles/r4_streamk_probe.log).
 """
 from __future__ import annotations
+
+from vgate.ops import PATH_KX
 
 PLANS: dict[tuple[int, int, str, str], tuple] = {
     # Llama-3-70B TP = 8, one rank, batch 8, ctx 128: round-5 in-context sweep with the register-stationary
@@ -38,7 +40,7 @@ PLANS: dict[tuple[int, int, str, str], tuple] = {
     # profiles/r5_dense_kx_sweep.log). qkv / o_proj / down_proj stay on the tile kernels there.
     (17920, 1536, "silu", "dense"): ("kx", 0, 0, 0),
     # Qwen2.5-1.5B AWQ int4: no entries — every int4 decode GEMM runs the register-stationary kernel
-    # (csrc/kernels/gemm_awq_kx.hip) on its own grid rule (round 3's awq_stream / wide plans:
+    # (csrc/kernels/gemm_kx.h / gemm_kx_q4.hip) on its own grid rule (round 3's awq_stream / wide plans:
     # profiles/r3_awq_decode_sweep.log)
 }
 
@@ -53,7 +55,7 @@ def apply(model) -> int:
             if p[0] == "sk":
                 lin.dec_sk = tuple(p[1:])
             elif p[0] == "kx":
-                lin.dec_path = 4
+                lin.dec_path = PATH_KX
                 lin.dec_waves, lin.dec_splitk, lin.dec_ntb = p[1:]
             else:
                 lin.dec_waves, lin.dec_splitk, lin.dec_ntb = p

@@ -1,0 +1,196 @@
+"""Weight packing for the GEMM kernels and the :class:`Linear` that holds a layer in kernel-ready form."""
+from __future__ import annotations
+
+import torch
+
+from . import reference as ref
+from ._native import PATH_AUTO
+
+
+def pack_weight(w: torch.Tensor) -> torch.Tensor:
+    """[N, K] -> fragment-major [N/16, K/32, 4, 16, 8] (see csrc/kernels/gemm.hip)."""
+    N, K = w.shape
+    assert N % 16 == 0 and K % 32 == 0, (N, K)
+    return w.reshape(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+
+
+def unpack_weight(wp: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    return wp.reshape(N // 16, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(N, K)
+
+
+def interleave_gate_up(w_gate: torch.Tensor, w_up: torch.Tensor) -> torch.Tensor:
+    """Rows ordered [G0 U0 G1 U1 ...] in 16-row tiles for the fused SiLU*mul epilogue."""
+    I, K = w_gate.shape
+    assert I % 16 == 0
+    return torch.stack([w_gate.reshape(I // 16, 16, K), w_up.reshape(I // 16, 16, K)], 1).reshape(2 * I, K)
+
+
+def unpack_awq(packed: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of :func:`pack_awq`: int32 [N/16, K/128, 64, 4] -> int4 values [N, K] (int32)."""
+    w = packed.to(torch.int64) & 0xFFFFFFFF
+    w = w.reshape(N // 16, K // 128, 4, 16, 4)  # nt, kq, g, r, u
+    j = torch.arange(8, dtype=torch.int64, device=packed.device)
+    shifts = (j & 1) * 16 + (j >> 1) * 4
+    q = (w[..., None] >> shifts) & 0xF  # nt, kq, g, r, u, j
+    return q.permute(0, 3, 1, 4, 2, 5).reshape(N, K).to(torch.int32)
+
+
+def pack_awq(qint: torch.Tensor) -> torch.Tensor:
+    """int4 values [N, K] (0..15) -> int32 [N/16, K/128, 64, 4]; word u of lane l holds the 8
+    values W[16nt + (l&15)][128kq + 32u + 8(l>>4) + j], j = 0..7, with the EVEN j in the low
+    half-word and the odd j in the high one: value j at bit (16 if j odd) + 4 (j >> 1).
+    Then (word >> 4d) & 0x000F000F | 0x43004300 is the bf16 pair (128 + v_2d, 128 + v_2d+1):
+    two VALU ops per MFMA operand dword (gemm.hip, AWQ decode kernel)."""
+    N, K = qint.shape
+    assert N % 16 == 0 and K % 128 == 0
+    q = qint.to(torch.int64).reshape(N // 16, 16, K // 128, 4, 4, 8)  # nt, r, kq, u, g, j
+    q = q.permute(0, 2, 4, 1, 3, 5)  # nt, kq, g, r, u, j  -> lane = g*16 + r
+    j = torch.arange(8, dtype=torch.int64, device=qint.device)
+    shifts = (j & 1) * 16 + (j >> 1) * 4
+    words = (q << shifts).sum(-1)  # [nt, kq, g, r, u]
+    words = words.reshape(N // 16, K // 128, 64, 4)
+    words = torch.where(words >= 2**31, words - 2**32, words)
+    return words.to(torch.int32).contiguous()
+
+
+def pack_awq_sz(scales: torch.Tensor, sz: torch.Tensor) -> torch.Tensor:
+    """Group scales in the AWQ decode kernels' fragment order (csrc/kernels/gemm_kx.h /
+    gemm_kx_q4.hip, gemm_awq_mid.hip):
+    [N/16][K/128][4 lane groups][s(4 cols), s*z(4 cols)] bf16, so the lanes of a 16-lane group load
+    their 4 columns' scale AND zero term with ONE 16-B load per (tile, k-quad). Group 128 only."""
+    G, N = scales.shape
+    s4 = scales.t().reshape(N // 16, 4, 4, G).permute(0, 3, 1, 2)  # [nt][g][lane group][4]
+    z4 = sz.t().reshape(N // 16, 4, 4, G).permute(0, 3, 1, 2)
+    return torch.cat([s4, z4], dim=-1).to(torch.bfloat16).contiguous()  # [nt][g][4][8]
+
+
+def row_permutation(N: int, layout: str) -> torch.Tensor | None:
+    """Row order of the packed weight for a fused epilogue (None = identity).
+
+    silu: tile t = gate rows 8t..8t+7 then up rows 8t..8t+7 (rows [gate; up] in the dense
+          matrix), so one 16-row tile holds 8 SiLU pairs on lanes l, l^32 and a decode block
+          can own a single tile (gemm_epilogue.h);
+    qkv : per 128-wide head, tile t (t = 0..7) = rows 8t..8t+7 then their NeoX rotation
+          partners 64+8t..64+8t+7, so one 16-row tile holds both halves of 8 rotation pairs
+          (the GEMM epilogue exchanges them across lanes l, l^32; csrc/kernels/gemm.hip qkv_col).
+    """
+    if layout == "silu":
+        I = N // 2
+        assert I % 8 == 0
+        t = torch.arange(2 * I).reshape(2, I // 8, 8).transpose(0, 1)
+        return t.reshape(-1)
+    if layout == "qkv":
+        assert N % 128 == 0
+        heads = N // 128
+        tile = torch.arange(128).reshape(2, 8, 8).permute(1, 0, 2).reshape(8, 16)
+        t = torch.arange(heads)[:, None, None] * 128 + tile[None]
+        return t.reshape(-1)
+    return None
+
+
+class Linear:
+    """A linear layer's weights in kernel-ready form.
+
+    layout: "plain" | "silu" (rows [gate; up] -> out = silu(gate) * up)
+            | "qkv" (rows [q; k; v], heads of 128: fused bias + RoPE + KV-cache write).
+    Dense bf16 weights or AWQ int4 (``awq={"qint", "scales", "zeros", "group"}``).
+    On GPU only the fragment-packed copy is kept; on CPU the dense matrix (reference path).
+    """
+
+    def __init__(self, w: torch.Tensor | None, bias: torch.Tensor | None = None, kind: str = "plain",
+                 awq: dict | None = None, layout: str | None = None):
+        if kind in ("silu", "qkv"):
+            layout, kind = kind, "dense"
+        self.layout = layout or (awq.get("layout", "plain") if awq else "plain")
+        if awq is not None and awq.get("silu"):
+            self.layout = "silu"
+        self.kind = "awq" if awq is not None else "dense"
+        self.bias = bias
+        self.norm_gamma = None  # RMSNorm weight folded into the packed copy (see fold_norm)
+        # decode-GEMM decomposition for M <= 16 steps (0 = the launcher's heuristic): set by the
+        # model from the measured per-shape table (vgate/models/decode_plans.py)
+        self.dec_waves = 0
+        self.dec_splitk = 0
+        self.dec_sk = None  # stream-K decode kernel: None = STREAMK_DECODE, or (waves, blocks/CU, group)
+        self.dec_ntb = 0
+        self.dec_path = PATH_AUTO  # PATH_KX: the register-stationary decode kernel (csrc/kernels/gemm_kx.h)
+        # prefill (M >= 128) tile / K-slice choice per M bucket, measured at engine start-up
+        # (tune_prefill); empty = the launcher's heuristic
+        self.prefill_plan: dict[int, tuple[int, int]] = {}
+        self.w = self.wp = None  # the dense matrix on the CPU, the packed copy on a GPU
+        self.szp = None  # AWQ group 128 on a GPU: the packed (scale, scale * zero) operand (pack_awq_sz)
+        if self.kind == "awq":
+            q = awq["qint"]
+            self.N, self.K = q.shape
+            self.group = awq["group"]
+            dev = awq["scales"].device
+            perm = row_permutation(self.N, self.layout)
+            scales, zeros = awq["scales"], awq["zeros"]
+            if dev.type == "cuda":
+                q = q.to(dev)
+                if perm is not None:
+                    pd = perm.to(dev)
+                    q, scales, zeros = q[pd], scales[:, pd], zeros[:, pd]
+                self.wp = pack_awq(q)
+                self.scales = scales.to(torch.bfloat16).contiguous()
+                self.zeros = (scales.float() * zeros.float()).to(torch.bfloat16).contiguous()
+                if self.group == 128:
+                    self.szp = pack_awq_sz(self.scales, self.zeros)
+            else:
+                self.w = ref.awq_dequant_ref(q, scales, zeros, self.group)
+            return
+        self.N, self.K = w.shape
+        if w.is_cuda:
+            perm = row_permutation(self.N, self.layout)
+            self.wp = pack_weight(w[perm.to(w.device)] if perm is not None else w)
+        else:
+            self.w = w
+
+    def fold_norm(self, gamma: torch.Tensor) -> bool:
+        """Fold the preceding RMSNorm's weight into the packed matrix: W'[n,k] = W[n,k]*g[k].
+
+        The fused GEMM then applies only the per-row scale rsqrt(mean(x^2)+eps) (deferred, in
+        the epilogue) and streams no gamma bytes. GPU bf16 weights only; returns whether folded.
+        """
+        if self.kind != "dense" or self.wp is None or self.norm_gamma is not None:
+            return False
+        g = gamma.to(self.wp.device, torch.float32).reshape(1, self.K // 32, 4, 1, 8)
+        self.wp.copy_((self.wp.float() * g).to(torch.bfloat16))
+        self.norm_gamma = gamma.detach().clone()
+        return True
+
+    def _original_rows(self, w: torch.Tensor) -> torch.Tensor:
+        """Undo the layout's row permutation of an unpacked [N, K] matrix."""
+        perm = row_permutation(self.N, self.layout)
+        if perm is None:
+            return w
+        out = torch.empty_like(w)
+        out[perm.to(w.device)] = w
+        return out
+
+    @property
+    def out_features(self) -> int:
+        return self.N // 2 if self.layout == "silu" else self.N
+
+    def dense_weight(self) -> torch.Tensor:
+        """[N, K] in the ORIGINAL row order (references / checkpoint export)."""
+        if self.w is not None:
+            return self.w
+        if self.kind == "awq":  # dequantised bf16 v * s - s * z (references)
+            q = unpack_awq(self.wp, self.N, self.K)  # permuted row order, like scales / zeros
+            g = torch.arange(self.K, device=q.device) // self.group
+            w = (q.float() * self.scales.float()[g].t() - self.zeros.float()[g].t()).to(torch.bfloat16)
+            return self._original_rows(w)
+        w = unpack_weight(self.wp, self.N, self.K)
+        if self.norm_gamma is not None:  # un-fold (approximate: W' was rounded to bf16)
+            w = (w.float() / self.norm_gamma.to(w.device, torch.float32)[None]).to(torch.bfloat16)
+        return self._original_rows(w)
+
+    def nbytes(self) -> int:
+        """Bytes a decode step streams."""
+        if self.kind == "awq" and self.w is None:
+            n = self.wp.numel() * 4 + self.scales.numel() * 4  # int4 + (s, s*z) bf16 per group
+            return n + (self.szp.numel() * 2 if self.szp is not None else 0)
+        t = self.wp if self.wp is not None else self.w
+        return t.numel() * t.element_size()
+
