@@ -152,6 +152,8 @@ extern int g_flash_prefill;
 constexpr int FL_KV = 64;
 constexpr int FL_STAGE = 2 * FL_KV * D_ * 2;  // K + V of one chunk (32 KiB)
 constexpr int FL_NST_MAX = 4;                 // ring stages (<= 128 KiB: one block per CU)
+// K split hand-off: 16-B words per lane and part for CT column tiles (fp32 o / l: 8 each, then (m, l))
+__host__ __device__ constexpr int FL_SPLIT_WORDS(int ct) { return ct * 8 + 1; }
 
 // f32 max of values known not to be NaN: one v_max / v_max3 each (fmaxf's IEEE-mode lowering
 // canonicalises every MFMA-produced input first: an extra v_max x, x per value)
@@ -423,11 +425,13 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the look-ahead DMAs drained before the block exits
   if (split) {
-    // The parts meet per wave. Each rounds its partial to bf16 normalised by its own sum (o / l),
-    // (m, l) in fp32, and takes the wave's ticket first: the nsp - 1 early arrivers publish
-    // (16-B sc1 stores, drain, +1 on the ready word) and exit; the last waits for ready = nsp - 1
-    // (the others never wait, so they always get there), re-arms both words and merges every
-    // part's ROUNDED partial in fixed part order: the result does not depend on arrival order.
+    // The parts meet per wave. Each hands over its partial normalised by its own sum (o / l) and
+    // (m, l), all fp32 (rounded to bf16, a partial carried its rounding at ITS magnitude into the
+    // merge: two halves that cancel left up to 2^-9 of a half in a result near zero), and takes the
+    // wave's ticket first: the nsp - 1 early arrivers publish (16-B sc1 stores, drain, +1 on the ready
+    // word) and exit; the last waits for ready = nsp - 1 (the others never wait, so they always get
+    // there), re-arms both words and merges every part's partial in fixed part order, its own as the
+    // very values it would have published: the result does not depend on arrival order.
     // Slot: the leader's rank over the step (every earlier sequence holds ceil(qlen / QPB)
     // leaders), KV head, wave; the host sized fl_ws for (tiles 16 / QPB + S + 1) Hkv NW <= 32768
     // slots of zs parts.
@@ -442,21 +446,16 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
     uint32_t* ticket = a.fl_tickets + wslot;
     uint32_t* ready = a.fl_tickets + 32768 + wslot;
     float ll[CT];
-    uint4 pw[CT][4];  // this part's o / l, bf16, mt pairs
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
+    for (int ct = 0; ct < CT; ++ct) {  // this part's o / l, in place
       ll[ct] = l[ct];
       ll[ct] += xor16(ll[ct]);
       ll[ct] += xor32(ll[ct]);
       const float inv = ll[ct] > 0.f ? 1.f / ll[ct] : 0.f;
 #pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const f32x4 x0 = o[ct][2 * w], x1 = o[ct][2 * w + 1];
-        pw[ct][w] = make_uint4(pack_bf2(x0[0] * inv, x0[1] * inv), pack_bf2(x0[2] * inv, x0[3] * inv),
-                               pack_bf2(x1[0] * inv, x1[1] * inv), pack_bf2(x1[2] * inv, x1[3] * inv));
-      }
+      for (int mt = 0; mt < 8; ++mt) o[ct][mt] *= inv;
     }
-    constexpr uint32_t PW = CT * 4 + 1;  // 16-B words per lane and part: the bf16 partial, then (m, l) pairs
+    constexpr uint32_t PW = FL_SPLIT_WORDS(CT);  // 16-B words per lane and part: the fp32 partial, then (m, l) pairs
     const uint32_t lane_off = lane * 16u;
     auto part_off = [&](int p) { return (wslot * (uint32_t)zs + (uint32_t)p) * PW * 1024u + lane_off; };
     uint32_t old = 0;
@@ -467,9 +466,8 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-        for (int w = 0; w < 4; ++w)
-          st_sc1_x4(a.fl_ws, off + (uint32_t)(ct * 4 + w) * 1024u, __builtin_bit_cast(f32x4, pw[ct][w]));
-      st_sc1_x4(a.fl_ws, off + CT * 4 * 1024u, f32x4{m[0], ll[0], m[CT - 1], ll[CT - 1]});
+        for (int mt = 0; mt < 8; ++mt) st_sc1_x4(a.fl_ws, off + (uint32_t)(ct * 8 + mt) * 1024u, o[ct][mt]);
+      st_sc1_x4(a.fl_ws, off + CT * 8 * 1024u, f32x4{m[0], ll[0], m[CT - 1], ll[CT - 1]});
       drain_stores();
       if (lane == 0) __hip_atomic_fetch_add(ready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return;
@@ -495,10 +493,8 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
     f32x4 ml[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
-      ml[p] = (p < nsp && p != z) ? ld_sc1_x4(a.fl_ws, part_off(p) + CT * 4 * 1024u)
+      ml[p] = (p < nsp && p != z) ? ld_sc1_x4(a.fl_ws, part_off(p) + CT * 8 * 1024u)
                                   : f32x4{m[0], ll[0], m[CT - 1], ll[CT - 1]};
-    auto lo_f = [](uint32_t u) { return __uint_as_float(u << 16); };
-    auto hi_f = [](uint32_t u) { return __uint_as_float(u & 0xffff0000u); };
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       float mm = -INFINITY;
@@ -513,26 +509,19 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
         lt += wt[p];
       }
       const float inv = lt > 0.f ? 1.f / lt : 0.f;
-      float acc[32];
+      f32x4 acc[8];
 #pragma unroll
-      for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+      for (int mt = 0; mt < 8; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         if (p >= nsp) continue;
-        uint4 q4[4];
+        f32x4 v[8];
 #pragma unroll
-        for (int w = 0; w < 4; ++w)
-          q4[w] = p == z ? pw[ct][w] : __builtin_bit_cast(uint4, ld_sc1_x4(a.fl_ws, part_off(p) + (uint32_t)(ct * 4 + w) * 1024u));
+        for (int mt = 0; mt < 8; ++mt)
+          v[mt] = p == z ? o[ct][mt] : ld_sc1_x4(a.fl_ws, part_off(p) + (uint32_t)(ct * 8 + mt) * 1024u);
         const float wp = wt[p] * inv;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const uint32_t u[4] = {q4[w].x, q4[w].y, q4[w].z, q4[w].w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            acc[8 * w + 2 * k] += lo_f(u[k]) * wp;
-            acc[8 * w + 2 * k + 1] += hi_f(u[k]) * wp;
-          }
-        }
+        for (int mt = 0; mt < 8; ++mt) acc[mt] += v[mt] * wp;
       }
       const int qi = qw0 + 16 * ct + col;
       if (qi >= qhi) continue;
@@ -540,8 +529,8 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
 #pragma unroll
       for (int mt = 0; mt < 8; ++mt) {
         uint2 pk;
-        pk.x = pack_bf2(acc[4 * mt], acc[4 * mt + 1]);
-        pk.y = pack_bf2(acc[4 * mt + 2], acc[4 * mt + 3]);
+        pk.x = pack_bf2(acc[mt][0], acc[mt][1]);
+        pk.y = pack_bf2(acc[mt][2], acc[mt][3]);
         *reinterpret_cast<uint2*>(a.out + orow + 16 * mt + 4 * g4) = pk;
       }
     }
@@ -643,7 +632,7 @@ void launch_attention(const AttnArgs& a, int dec_seqs, hipStream_t st) {
       const size_t cap = (size_t)cu_count(1) * (fc.ct == 2 ? 1 : 2);
       if (blocks < 2 * cap) zs = 2;
       if (blocks * 4 <= cap) zs = 4;
-      if (slots > 32768 || slots * zs * (fc.ct * 4 + 1) * 1024 > f.fl_ws_bytes) zs = 1;
+      if (slots > 32768 || slots * zs * FL_SPLIT_WORDS(fc.ct) * 1024 > f.fl_ws_bytes) zs = 1;
     }
     const dim3 grid(a.Hkv * zs, tiles + dec_rows, 1), block(64 * fc.nw);
     f.tl = tl_take("attn_flash", (tiles + dec_rows) * a.Hkv * zs);

@@ -221,7 +221,10 @@ __device__ __forceinline__ void decode_block(const AttnArgs& a, int s, int h, in
   const bool cok = col < G;
   uint4 qf[4];  // (FUSED: from the producer's granules, after the wait)
   if constexpr (!FUSED) {
-    const bf16_t* qp = a.q + (size_t)qbeg * a.q_stride + (size_t)(h * G + (cok ? col : 0)) * D_ + 8 * (lane >> 4);
+    // a sequence that is not decode work (the block exits below) must not steer this early load: an
+    // empty sequence at the end of a step (the padding of a graph bucket) has qbeg = the row BEHIND q
+    const int qrow = qend - qbeg == 1 ? qbeg : 0;
+    const bf16_t* qp = a.q + (size_t)qrow * a.q_stride + (size_t)(h * G + (cok ? col : 0)) * D_ + 8 * (lane >> 4);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) qf[kk] = cok ? *reinterpret_cast<const uint4*>(qp + 32 * kk) : make_uint4(0, 0, 0, 0);
   }

@@ -236,7 +236,7 @@ struct AttnArgs {
   unsigned long long* dbg_ts;
   unsigned long long* tl;  // launch timeline slot (set by the launcher), or null
   // flash prefill K split (attention.hip attn_flash_kernel, two blocks per KV head): the two halves of a long
-  // causal range meet through bf16 partials + fp32 (m, l) in fl_ws and a zeroed, self-resetting
+  // causal range meet through fp32 partials + (m, l) in fl_ws and a zeroed, self-resetting
   // ticket + ready word per (leader, KV head, wave) (fl_tickets: 65536 words); null -> no split
   float* fl_ws = nullptr;
   size_t fl_ws_bytes = 0;
