@@ -300,6 +300,28 @@ void launch_logits_process(float* logits, int ldl, int S, int V, const int32_t* 
 int sample_segments(int B, int V);
 void set_sample_nseg(int n);  // cap on segments per row, 1..SAMPLE_GRAN_SEGS (1 = one block per row)
 
+// Top-k log-softmax of the sampled rows, after the sampler (logprobs.hip): two launches, no in-launch
+// hand-off. Row r with k_rows[r] < 0 is skipped (its record is left as it is); otherwise its record is
+// {chosen id, logprob, 20 x (id, logprob), 2 pad words}: the log-softmax at temperature 1 of the row as
+// the sampler read it, the chosen id = tokens[r] clamped into [0, V), the first min(k_rows[r], 20)
+// entries the row's most likely tokens by (logit descending, id ascending), the rest (-1, 0.0).
+constexpr int LOGPROB_TOP = 20;                          // alternatives per row
+constexpr int LOGPROB_SEGS = 32;                         // max segments per row
+constexpr int LOGPROB_PART_WORDS = 2 + 2 * LOGPROB_TOP;  // {m, l, 20 x (value, id)} per (row, segment)
+constexpr int LOGPROB_REC_WORDS = 44;                    // record per row (176 B)
+struct LogprobArgs {
+  const float* logits;    // [S, V] f32, row stride ldl (a multiple of 4, 16-B aligned rows)
+  int ldl;
+  int S;
+  int V;
+  const int32_t* tokens;  // [S] the sampler's output
+  const int32_t* k_rows;  // [S]
+  float* part;            // [S, LOGPROB_SEGS, LOGPROB_PART_WORDS] private partials
+  int32_t* rec;           // [S, LOGPROB_REC_WORDS]
+};
+int logprob_segments(int S, int V);
+void launch_logprobs(const LogprobArgs& a, hipStream_t st);
+
 // Custom one-shot all-reduce over IPC-mapped peer buffers (xGMI).
 struct AllReduceArgs {
   void* const* peers;     // device array of world_size peer buffer pointers

@@ -29,23 +29,6 @@
 
 namespace vgate {
 
-// Lane exchange on the VALU (no LDS round trip per step, unlike __shfl_xor's ds_bpermute): DPP
-// quad permutes for partners 1 and 2, row rotations by 4 and 8 (after the quad steps every lane of
-// a quad holds the quad's merge, so rotations complete the 16-lane row), permlane swaps for 16 / 32.
-template <int K>
-__device__ __forceinline__ uint32_t lane_x(uint32_t v) {
-  if constexpr (K == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  else if constexpr (K == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, false);  // [2,3,0,1]
-  else if constexpr (K == 4) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xf, 0xf, false);  // row_ror:4
-  else if constexpr (K == 8) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xf, 0xf, false);  // row_ror:8
-  else if constexpr (K == 16) {
-    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return (threadIdx.x & 16) ? r[0] : r[1];
-  } else {
-    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return (threadIdx.x & 32) ? r[0] : r[1];
-  }
-}
 template <int K>
 __device__ __forceinline__ void acc_step(Acc& a, float c) {
   const float om = __uint_as_float(lane_x<K>(__float_as_uint(a.mx)));

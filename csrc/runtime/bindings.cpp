@@ -507,6 +507,36 @@ void process_logits(Tensor& logits, const Tensor& row_off, const Tensor& pend, c
                                pv, nprev, cur_stream());
 }
 
+// Top-k log-softmax records of the sampled rows (csrc/kernels/logprobs.hip), after the sampler.
+void logprobs(const Tensor& logits, const Tensor& tokens, const Tensor& k_rows, Tensor& part, Tensor& rec) {
+  CHECK_DEV(logits); CHECK_DEV(tokens); CHECK_DEV(k_rows); CHECK_DEV(part); CHECK_DEV(rec);
+  CHECK_DT(logits, torch::kFloat32); CHECK_DT(tokens, torch::kInt32); CHECK_DT(k_rows, torch::kInt32);
+  CHECK_DT(part, torch::kFloat32); CHECK_DT(rec, torch::kInt32);
+  CHECK_LASTDIM(logits);
+  TORCH_CHECK(logits.dim() == 2, "logprobs: logits [S, V]");
+  vgate::LogprobArgs a{};
+  a.logits = reinterpret_cast<const float*>(logits.data_ptr());
+  a.ldl = (int)logits.stride(0);
+  a.S = (int)logits.size(0);
+  a.V = (int)logits.size(1);
+  TORCH_CHECK(a.V >= 1 && a.ldl % 4 == 0 && a.ldl >= a.V && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "logprobs: the row stride must be a multiple of 4 floats (16-B aligned rows)");
+  TORCH_CHECK(tokens.is_contiguous() && k_rows.is_contiguous() && part.is_contiguous() && rec.is_contiguous(),
+              "logprobs: contiguous tokens, k_rows, partials and records");
+  TORCH_CHECK(tokens.numel() >= a.S && k_rows.numel() >= a.S, "logprobs: tokens [S], k_rows [S]");
+  TORCH_CHECK(part.numel() >= (int64_t)a.S * vgate::LOGPROB_SEGS * vgate::LOGPROB_PART_WORDS &&
+                  reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
+              "logprobs: partials need S x ", vgate::LOGPROB_SEGS, " x ", vgate::LOGPROB_PART_WORDS, " floats");
+  TORCH_CHECK(rec.numel() >= (int64_t)a.S * vgate::LOGPROB_REC_WORDS && reinterpret_cast<uintptr_t>(rec.data_ptr()) % 16 == 0,
+              "logprobs: records need S x ", vgate::LOGPROB_REC_WORDS, " int32");
+  a.tokens = reinterpret_cast<const int32_t*>(tokens.data_ptr());
+  a.k_rows = reinterpret_cast<const int32_t*>(k_rows.data_ptr());
+  a.part = reinterpret_cast<float*>(part.data_ptr());
+  a.rec = reinterpret_cast<int32_t*>(rec.data_ptr());
+  c10::DeviceGuard guard(logits.device());
+  vgate::launch_logprobs(a, cur_stream());
+}
+
 // Warm the memory-side cache with a tensor's bytes (default-policy read sweep, nothing written).
 // Copy the first `nbytes` (rounded up to 16, within both tensors) between a pinned host tensor and
 // a device tensor with a kernel on the current stream (no SDMA engine hand-off, see elementwise.hip).
@@ -693,6 +723,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("process_logits", &process_logits, "repetition / presence / frequency penalties + logit_bias, in place",
         py::arg("logits"), py::arg("row_off"), py::arg("pend"), py::arg("par"), py::arg("entries"),
         py::arg("prev") = py::none());
+  m.def("logprobs", &logprobs, "top-k log-softmax records of the sampled rows (two launches, after the sampler)",
+        py::arg("logits"), py::arg("tokens"), py::arg("k_rows"), py::arg("part"), py::arg("rec"));
+  m.def("logprob_segments", &vgate::logprob_segments, "blocks per row the logprob part kernel uses for (S, V)");
+  m.attr("LOGPROB_TOP") = vgate::LOGPROB_TOP;
+  m.attr("LOGPROB_SEGS") = vgate::LOGPROB_SEGS;
+  m.attr("LOGPROB_PART_WORDS") = vgate::LOGPROB_PART_WORDS;
+  m.attr("LOGPROB_REC_WORDS") = vgate::LOGPROB_REC_WORDS;
   m.def("sample_segments", &vgate::sample_segments, "blocks per row the sampler uses for (B, V)");
   m.def("set_sample_nseg", &vgate::set_sample_nseg, "cap the sampler's segments per row (1 = one block per row)");
   m.attr("SAMPLE_WS_WORDS") = vgate::SAMPLE_WS_WORDS;

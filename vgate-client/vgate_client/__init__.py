@@ -9,13 +9,13 @@
 from .client import AsyncChatStream, AsyncVGate, SyncChatStream, VGate
 from .exceptions import AuthenticationError, ConnectionError, RateLimitError, ServerError, VGateError
 from .models import (ChatCompletion, ChatCompletionChunk, ChatCompletionChunkChoice, ChatCompletionDelta,
-                     ChatMessage, Choice, EmbeddingData, EmbeddingResponse, HealthResponse, RateLimitInfo,
-                     ResponseMessage, Usage)
+                     ChatMessage, Choice, ChoiceLogprobs, EmbeddingData, EmbeddingResponse, HealthResponse, RateLimitInfo,
+                     ResponseMessage, TokenLogprob, TopLogprob, Usage)
 
 __version__ = "0.1.0"
 __all__ = [
     "VGate", "AsyncVGate", "SyncChatStream", "AsyncChatStream",
     "ChatCompletion", "ChatCompletionChunk", "ChatCompletionChunkChoice", "ChatCompletionDelta", "Choice",
     "ResponseMessage", "EmbeddingResponse", "EmbeddingData", "HealthResponse", "Usage", "RateLimitInfo",
-    "ChatMessage", "VGateError", "AuthenticationError", "RateLimitError", "ServerError", "ConnectionError",
+    "ChatMessage", "ChoiceLogprobs", "TokenLogprob", "TopLogprob", "VGateError", "AuthenticationError", "RateLimitError", "ServerError", "ConnectionError",
 ]

@@ -111,7 +111,8 @@ def _headers(api_key: Optional[str]) -> dict:
     return h
 
 
-_CONTROLS = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias", "seed", "top_k")
+_CONTROLS = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias", "seed", "top_k",
+             "logprobs", "top_logprobs")
 
 
 def _chat_req(model, messages, temperature, top_p, max_tokens, stream=False, **controls) -> dict:
@@ -174,22 +175,26 @@ class _SyncChat:
                max_tokens: int = 256, presence_penalty: Optional[float] = None,
                frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                logit_bias: Optional[dict] = None, seed: Optional[int] = None,
-               top_k: Optional[int] = None) -> ChatCompletion:
+               top_k: Optional[int] = None, logprobs: Optional[bool] = None,
+               top_logprobs: Optional[int] = None) -> ChatCompletion:
         data = self._c._request("POST", "/v1/chat/completions",
                                 json=_chat_req(model, messages, temperature, top_p, max_tokens,
                                                presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                                               repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k))
+                                               repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k,
+                                               logprobs=logprobs, top_logprobs=top_logprobs))
         return ChatCompletion.model_validate(data)
 
     def stream(self, *, model: str, messages: list[dict], temperature: float = 0.7, top_p: float = 0.9,
                max_tokens: int = 256, presence_penalty: Optional[float] = None,
                frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                logit_bias: Optional[dict] = None, seed: Optional[int] = None,
-               top_k: Optional[int] = None) -> SyncChatStream:
+               top_k: Optional[int] = None, logprobs: Optional[bool] = None,
+               top_logprobs: Optional[int] = None) -> SyncChatStream:
         return SyncChatStream(self._c._stream(_chat_req(
             model, messages, temperature, top_p, max_tokens, True,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-            repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k)))
+            repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k,
+            logprobs=logprobs, top_logprobs=top_logprobs)))
 
 
 class _SyncEmbeddings:
@@ -285,23 +290,27 @@ class _AsyncChat:
                      max_tokens: int = 256, presence_penalty: Optional[float] = None,
                      frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                      logit_bias: Optional[dict] = None, seed: Optional[int] = None,
-                     top_k: Optional[int] = None) -> ChatCompletion:
+                     top_k: Optional[int] = None, logprobs: Optional[bool] = None,
+                     top_logprobs: Optional[int] = None) -> ChatCompletion:
         data = await self._c._request("POST", "/v1/chat/completions",
                                       json=_chat_req(model, messages, temperature, top_p, max_tokens,
                                                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                                                     repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k))
+                                                     repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k,
+                                                     logprobs=logprobs, top_logprobs=top_logprobs))
         return ChatCompletion.model_validate(data)
 
     def stream(self, *, model: str, messages: list[dict], temperature: float = 0.7, top_p: float = 0.9,
                max_tokens: int = 256, presence_penalty: Optional[float] = None,
                frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                logit_bias: Optional[dict] = None, seed: Optional[int] = None,
-               top_k: Optional[int] = None) -> AsyncChatStream:
+               top_k: Optional[int] = None, logprobs: Optional[bool] = None,
+               top_logprobs: Optional[int] = None) -> AsyncChatStream:
         """Not a coroutine: returns the stream immediately (``async for`` / ``async with``)."""
         return AsyncChatStream(self._c._stream(_chat_req(
             model, messages, temperature, top_p, max_tokens, True,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-            repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k)))
+            repetition_penalty=repetition_penalty, logit_bias=logit_bias, seed=seed, top_k=top_k,
+            logprobs=logprobs, top_logprobs=top_logprobs)))
 
 
 class _AsyncEmbeddings:

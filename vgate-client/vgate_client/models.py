@@ -25,6 +25,9 @@ class ChatCompletionRequest(BaseModel):
     logit_bias: Optional[dict[str, float]] = None
     seed: Optional[int] = None
     top_k: Optional[int] = None
+    # per-token log-probabilities (non-streaming): logprobs = True, top_logprobs = 0..20 alternatives
+    logprobs: Optional[bool] = None
+    top_logprobs: Optional[int] = None
 
 
 class EmbeddingRequest(BaseModel):
@@ -43,10 +46,28 @@ class ResponseMessage(BaseModel):
     content: str
 
 
+class TopLogprob(BaseModel):
+    token: str
+    logprob: float
+    bytes: Optional[list[int]] = None
+
+
+class TokenLogprob(BaseModel):
+    token: str
+    logprob: float  # -9999.0 stands for -inf (a token of probability zero)
+    bytes: Optional[list[int]] = None
+    top_logprobs: list[TopLogprob] = Field(default_factory=list)
+
+
+class ChoiceLogprobs(BaseModel):
+    content: Optional[list[TokenLogprob]] = None
+
+
 class Choice(BaseModel):
     index: int
     message: ResponseMessage
     finish_reason: Optional[str] = None
+    logprobs: Optional[ChoiceLogprobs] = None
 
 
 class ChatCompletion(BaseModel):

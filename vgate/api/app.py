@@ -29,7 +29,7 @@ from typing import Optional
 from fastapi import Depends, FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, Response, StreamingResponse
 from prometheus_client import CONTENT_TYPE_LATEST, generate_latest
-from pydantic import BaseModel, Field, field_validator
+from pydantic import BaseModel, Field, field_validator, model_validator
 
 from vgate import metrics as M
 from vgate.backends.base import InvalidSamplingParams
@@ -37,6 +37,8 @@ from vgate.batcher import RequestBatcher
 from vgate.config import VGateConfig, get_config, set_config
 from vgate.engine import VGateEngine
 from vgate.logging_config import get_logger, setup_logging
+from vgate.logprobs import annotate_result
+from vgate.logprobs import content as logprob_content
 from vgate.security import SecurityMiddleware
 from vgate.tracing import get_current_trace_id, init_tracing, shutdown_tracing
 from vgate.worker_registry import NoHealthyWorkersError
@@ -66,6 +68,18 @@ class ChatCompletionRequest(BaseModel):
     logit_bias: Optional[dict[str, float]] = None
     seed: Optional[int] = Field(None, ge=0)
     top_k: Optional[int] = Field(None, ge=1)
+    # per-token log-probabilities (OpenAI shape): logprobs = true reports every generated token's,
+    # top_logprobs = k (0..20) adds the k most likely tokens with theirs. Non-streaming only.
+    logprobs: Optional[bool] = None
+    top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+
+    @model_validator(mode="after")
+    def _check_logprobs(self):
+        if self.top_logprobs is not None and not self.logprobs:
+            raise ValueError("top_logprobs requires logprobs: true")
+        if self.logprobs and self.stream:
+            raise ValueError("logprobs with stream: true is not supported (streaming logprobs is out of scope)")
+        return self
 
     @field_validator("logit_bias")
     @classmethod
@@ -89,6 +103,8 @@ class ChatCompletionRequest(BaseModel):
             v = getattr(self, name)
             if v is not None:
                 out[name] = v
+        if self.logprobs:  # one key: the alternatives per token (0 = the chosen token's logprob only)
+            out["logprobs"] = self.top_logprobs or 0
         return out
 
 
@@ -276,11 +292,17 @@ async def chat_completion_json(st: "AppState", request: "ChatCompletionRequest")
         return 500, _error_body(str(e)), []
     pt = r.get("prompt_tokens", 0)
     ct = r.get("total_tokens", 0)
+    choice = {"index": 0, "message": {"role": "assistant", "content": r["text"]},
+              "finish_reason": r.get("finish_reason", "stop")}
+    if "logprobs" in extra:  # present whenever requested: null from a backend that returns none
+        lps = r.get("logprobs")
+        if lps is not None:
+            annotate_result(r, getattr(st.engine, "backend", None))
+            lps = {"content": logprob_content(lps)}
+        choice["logprobs"] = lps
     return 200, json.dumps({
         "id": "chatcmpl-" + os.urandom(4).hex(), "object": "chat.completion", "created": int(time.time()),
-        "model": request.model,
-        "choices": [{"index": 0, "message": {"role": "assistant", "content": r["text"]},
-                     "finish_reason": r.get("finish_reason", "stop")}],
+        "model": request.model, "choices": [choice],
         "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": ct + pt}}).encode(), []
 
 

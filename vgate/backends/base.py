@@ -55,7 +55,8 @@ class InferenceBackend(Protocol):
 
     def create_sampling_params(self, temperature: float, top_p: float, max_tokens: int, **extra) -> Any:
         """``extra``: the optional sampling controls of a request (repetition_penalty,
-        presence_penalty, frequency_penalty, logit_bias, seed, top_k); passed only when one is set."""
+        presence_penalty, frequency_penalty, logit_bias, seed, top_k, logprobs); passed only when one is set.
+        A backend that serves ``logprobs`` adds ``"logprobs"`` to its results (vgate/logprobs.py)."""
         ...
 
     def generate(self, prompts: List[str], sampling_params: Any) -> List[Dict[str, Any]]: ...

@@ -104,7 +104,7 @@ class NativeBackend:
                               repetition_penalty=float(sp.get("repetition_penalty", 1.0)),
                               presence_penalty=float(sp.get("presence_penalty", 0.0)),
                               frequency_penalty=float(sp.get("frequency_penalty", 0.0)),
-                              logit_bias=dict(sp.get("logit_bias") or {}))
+                              logit_bias=dict(sp.get("logit_bias") or {}), logprobs=sp.get("logprobs"))
 
     def _add(self, rid: str, prompt: str, sampling_params: Any, cb, **kw):
         """Queue a request; sampling controls the engine refuses (SamplingParams validation, a
@@ -121,9 +121,17 @@ class NativeBackend:
         ttft = (seq.first_token_time - seq.arrival) if seq.first_token_time else 0.0
         gen = (seq.finish_time - seq.first_token_time) if (seq.first_token_time and seq.finish_time) else 0.0
         wall = (seq.finish_time - seq.arrival) if seq.finish_time else 0.0
-        return {"text": seq.text, "token_ids": list(seq.output_ids), "num_tokens": len(seq.output_ids),
-                "prompt_tokens": len(seq.prompt_ids), "finish_reason": seq.finish_reason or "stop",
-                "metrics": {"ttft": ttft, "gen_time": gen, "wall_time": wall}}
+        res = {"text": seq.text, "token_ids": list(seq.output_ids), "num_tokens": len(seq.output_ids),
+               "prompt_tokens": len(seq.prompt_ids), "finish_reason": seq.finish_reason or "stop",
+               "metrics": {"ttft": ttft, "gen_time": gen, "wall_time": wall}}
+        lps = getattr(seq, "logprobs", None)
+        if lps is not None:  # only when requested: one entry per token of the returned text
+            from vgate.logprobs import annotate, result_entries
+            res["logprobs"] = result_entries(lps)
+            known = getattr(seq, "token_bytes", None)  # an engine core process sends its tokens' bytes along
+            if known is not None:
+                annotate(res["logprobs"], lambda t: known.get(t, b""))
+        return res
 
     # --------------------------------------------------------------- generate
     async def agenerate(self, prompt: str, sampling_params: Any) -> Dict[str, Any]:

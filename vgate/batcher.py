@@ -245,6 +245,8 @@ class RequestBatcher:
             out["prompt_tokens"] = br["prompt_tokens"]
         if "finish_reason" in br:
             out["finish_reason"] = br["finish_reason"]
+        if "logprobs" in br:
+            out["logprobs"] = br["logprobs"]
         return out
 
     def get_metrics(self) -> Dict[str, Any]:

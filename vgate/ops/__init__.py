@@ -17,8 +17,8 @@ import torch
 from . import reference as ref
 from ._native import (EPI_BF16, EPI_F32, EPI_QKV, EPI_SILU, PATH_AUTO, PATH_KX, PATH_MID, PATH_PREFILL,  # noqa: F401
                       PATH_STREAMK, native, native_available)
-from .buffers import (_TICKETS, _WS, attn_tickets, fault_word, qa_sync, reserve_awq_scratch,  # noqa: F401
-                      reset_handoffs, sample_workspace, sk_workspace, workspace)
+from .buffers import (_TICKETS, _WS, attn_tickets, fault_word, logprob_partials, qa_sync,  # noqa: F401
+                      reserve_awq_scratch, reset_handoffs, sample_workspace, sk_workspace, workspace)
 from .packing import (Linear, interleave_gate_up, pack_awq, pack_awq_sz, pack_weight, row_permutation,  # noqa: F401
                       unpack_awq, unpack_weight)
 from .tuner import (MEDIUM_DEFAULT, MID_BASE, MID_CANDIDATES, PREFILL_CANDIDATES,  # noqa: F401
@@ -363,6 +363,44 @@ def process_logits(logits, proc_view, prev_tokens=None):
     return logits
 
 
+LOGPROB_TOP = ref.LOGPROB_TOP
+LOGPROB_REC_WORDS = 44  # int32 words of a row's record: {chosen id, logprob, 20 x (id, logprob), 2 pad}
+
+
+def logprob_views(rec: torch.Tensor):
+    """(chosen_lp [S] f32, top_ids [S, 20] i32, top_lp [S, 20] f32) as views of records int32 [S, 44]."""
+    top = rec[:, 2: 2 + 2 * LOGPROB_TOP].unflatten(1, (LOGPROB_TOP, 2))
+    return rec[:, 1].view(torch.float32), top[:, :, 0], top[:, :, 1].view(torch.float32)
+
+
+def logprobs(logits, tokens, k_rows, out=None):
+    """Per-row log-probabilities after the sampler (csrc/kernels/logprobs.hip, two launches): the
+    log-softmax at temperature 1 of fp32 ``logits`` [S, V] as the sampler read them. ``tokens`` [S]
+    int32 are the sampled ids, ``k_rows`` [S] int32 the alternatives each row wants (0..20; < 0: the
+    row did not ask). Returns (chosen_lp [S] f32, top_ids [S, 20] i32, top_lp [S, 20] f32): the first
+    k_rows[r] entries of row r are its most likely tokens by (raw fp32 logit descending, id ascending),
+    the rest (-1, 0.0). They are views of ``out``, the rows' records int32 [>= S, 44] (allocated when
+    None; ``out[r, 0]`` is the chosen id); rows with k_rows < 0 are left untouched in it.
+    CPU: :func:`vgate.ops.reference.logprobs_ref` cast to fp32."""
+    S = logits.shape[0]
+    if out is None:
+        out = torch.zeros(S, LOGPROB_REC_WORDS, dtype=torch.int32, device=logits.device)
+    rec = out[:S]
+    if _gpu(logits):
+        native().logprobs(logits, tokens, k_rows, logprob_partials(logits.device, S), rec)
+        return logprob_views(rec)
+    lp, ids, tlp = ref.logprobs_ref(logits, tokens, k_rows)
+    asked = torch.as_tensor(k_rows).reshape(-1)[:S].cpu() >= 0
+    new = torch.zeros(S, LOGPROB_REC_WORDS, dtype=torch.int32)
+    new[:, 0] = torch.as_tensor(tokens).reshape(-1)[:S].to(torch.int32).clamp(0, logits.shape[1] - 1)
+    c, i, t = logprob_views(new)
+    c.copy_(lp.to(torch.float32))
+    i.copy_(ids.to(torch.int32))
+    t.copy_(tlp.to(torch.float32))
+    rec[asked] = new[asked]
+    return logprob_views(rec)
+
+
 def host_device_copy(dst: torch.Tensor, src: torch.Tensor, nbytes: int) -> None:
     """Copy the first ``nbytes`` between a pinned host tensor and a device tensor on the current
     stream. GPU: a kernel on the compute queue (csrc/kernels/elementwise.hip copy16_kernel), so the
@@ -384,6 +422,6 @@ __all__ = [
     "native", "native_available", "pack_weight", "unpack_weight", "interleave_gate_up", "pack_awq",
     "Linear", "linear", "attention", "workspace", "fault_word", "reset_handoffs",
     "row_permutation", "reserve_awq_scratch", "pack_awq_sz", "rmsnorm", "embedding", "rope_kv", "attention_decode", "attention_prefill",
-    "prefill_tiles", "sample", "softmax_scale", "ref", "host_device_copy", "tune_prefill", "apply_prefill_plans",
+    "prefill_tiles", "sample", "logprobs", "logprob_views", "softmax_scale", "ref", "host_device_copy", "tune_prefill", "apply_prefill_plans",
 ]
 

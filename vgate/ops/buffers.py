@@ -17,6 +17,7 @@ _TICKETS: dict = {}
 _FAULT: dict = {}
 _SWS: dict = {}
 _AWQ_SCRATCH: dict = {}
+_LP_PART: dict = {}
 # zeroed once and left zero by every launch; reset_handoffs returns them there after a fault (and the
 # ticket prefix of _WS)
 _HANDOFFS = (_FAULT, _QA_SYNC, _TICKETS, _SWS, _SKWS)
@@ -72,6 +73,20 @@ def sample_workspace(device) -> torch.Tensor:
     device; launchers.h SAMPLE_WS_*)."""
     return _per_device(_SWS, device,
                        lambda: torch.zeros(int(native().SAMPLE_WS_WORDS), dtype=torch.int32, device=device))
+
+
+def logprob_partials(device, rows: int) -> torch.Tensor:
+    """Private per-segment partials of the logprob kernels, fp32 [rows, 32, 42] (launchers.h LOGPROB_*):
+    written by the part launch, read by the merge launch right behind it on the same stream. Never read
+    before it is written, so not zeroed and not a hand-off buffer; allocated on the first logprob call
+    (at least 1024 rows, every sequence bucket) and only ever replaced by a larger one."""
+    key = _dev_key(device)
+    C = native()
+    words = int(C.LOGPROB_SEGS) * int(C.LOGPROB_PART_WORDS)
+    if key in _LP_PART and _LP_PART[key].numel() < rows * words:
+        del _LP_PART[key]
+    return _per_device(_LP_PART, device,
+                       lambda: torch.empty(max(rows, 1024) * words, dtype=torch.float32, device=device))
 
 
 def reserve_awq_scratch(device, numel: int) -> torch.Tensor:

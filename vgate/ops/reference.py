@@ -252,3 +252,42 @@ def process_logits_sparse(logits: torch.Tensor, row_off, pend, par, entries, pre
         row = logits[r]
         row[tok] = _penalise(row[tok], cnt, in_prompt, bias, par[r].float())
     return logits
+
+
+# ------------------------------------------------------------------------------------ logprobs
+LOGPROB_TOP = 20  # alternatives per row (csrc/kernels/launchers.h)
+
+
+def rank_keys(logits: torch.Tensor) -> torch.Tensor:
+    """int64 keys whose descending order is the logprob ranking of fp32 ``logits`` [..., V]: the raw
+    fp32 value descending, ties (-0.0 == 0.0 included) to the lower token id. Exact and unique."""
+    x = logits.detach().to(torch.float32).cpu() + 0.0  # -0.0 -> 0.0: equal values get equal bits
+    b = x.contiguous().view(torch.int32).to(torch.int64)
+    mono = torch.where(b >= 0, b, -(b & 0x7FFFFFFF) - 1)  # monotone in the float's value
+    ids = torch.arange(x.shape[-1], dtype=torch.int64)
+    return mono * (1 << 32) + ((1 << 31) - 1 - ids)
+
+
+def logprobs_ref(logits: torch.Tensor, tokens, k_rows):
+    """Oracle of the logprob kernels for fp32 ``logits`` [S, V]: a float64 log-softmax, the chosen
+    token's value (``tokens`` clamped into [0, V)), and per row the min(k_rows, 20) most likely tokens
+    ranked by the RAW fp32 logits (descending, ties to the lower id; :func:`rank_keys`), not by the
+    computed log-probabilities. Returns (chosen_lp [S] f64, top_ids [S, 20] i64, top_lp [S, 20] f64);
+    entries beyond a row's k are (-1, 0.0), and a row with k < 0 is all (-1, 0.0) with chosen_lp 0."""
+    x = logits.detach().to(torch.float32).cpu()
+    S, V = x.shape
+    tok = torch.as_tensor(tokens).to(torch.int64).cpu().reshape(-1)[:S].clamp(0, V - 1)
+    k = torch.as_tensor(k_rows).to(torch.int64).cpu().reshape(-1)[:S]
+    lp = torch.log_softmax(x.to(torch.float64), dim=-1)
+    n = min(LOGPROB_TOP, V)
+    order = torch.topk(rank_keys(x), n, dim=-1).indices  # keys are unique: the order is exact
+    chosen = lp.gather(1, tok[:, None])[:, 0]
+    top_ids = torch.full((S, LOGPROB_TOP), -1, dtype=torch.int64)
+    top_lp = torch.zeros(S, LOGPROB_TOP, dtype=torch.float64)
+    top_ids[:, :n] = order
+    top_lp[:, :n] = lp.gather(1, order)
+    off = torch.arange(LOGPROB_TOP)[None, :] >= k.clamp(max=LOGPROB_TOP)[:, None]
+    top_ids[off] = -1
+    top_lp[off] = 0.0
+    chosen = torch.where(k < 0, torch.zeros_like(chosen), chosen)
+    return chosen, top_ids, top_lp

@@ -30,7 +30,7 @@ from vgate.models.config import resolve_arch
 from vgate.models.transformer import DecoderModel
 from vgate.parallel.comm import TPGroup, init_tp
 from vgate.runtime.kv_cache import BLOCK_SIZE, KVCacheManager, allocate_kv_tensors
-from vgate.runtime.logits_proc import SeqProcState, check_request
+from vgate.runtime.logits_proc import SeqProcState, check_logprobs, check_request
 from vgate.runtime.model_runner import ModelRunner
 from vgate.runtime.sampling_params import SamplingParams
 from vgate.runtime.scheduler import Scheduler
@@ -340,6 +340,9 @@ class LLMEngine:
         if params.has_processors:
             check_request(params, self.arch.vocab_size, self.tp.size)
             seq.proc = SeqProcState(seq.prompt_ids, params.logit_bias)
+        if params.logprobs is not None:
+            check_logprobs(params, self.tp.size)
+            seq.logprobs = []
         seq.seed = params.seed if params.seed is not None else \
             (self.cfg.seed * 1000003 + zlib.crc32(request_id.encode())) & 0x7FFFFFFFFFFFFFFF
         if stream:
@@ -557,13 +560,14 @@ class LLMEngine:
             return 0
         t0 = time.perf_counter()
         check = self._consistency_due()
-        toks, samples = self.runner.execute(batch, check=check)
+        h = self.runner.launch(batch, check=check)
+        toks, samples = self.runner.collect(h), h.samples
         if check:
             self._consistency_exchange(batch.num_tokens, len(batch.items))
         self._check_collectives()
         for seq, n in batch.items:
             seq.num_computed += n
-        self._process(batch, toks, samples, t0, tc, resolve=False)
+        self._process(batch, toks, samples, t0, tc, resolve=False, lps=h.logprobs)
         return len(batch.items)
 
     def _step_async(self) -> int:
@@ -588,6 +592,8 @@ class LLMEngine:
             seq.num_computed += n
             if smp:
                 seq.output_ids.append(PENDING)
+                if seq.logprobs is not None:
+                    seq.logprobs.append(None)
                 seq.pending.append(len(seq.output_ids) - 1)
                 seq.pending_slot = i
         prev, self._inflight = self._inflight, (batch, h, tc)
@@ -606,11 +612,12 @@ class LLMEngine:
             toks = self.runner.collect(h)
         self._check_collectives()
         with range_("vgate.process"):
-            self._process(batch, toks, h.samples, h.t_launch, tc, resolve=True)
+            self._process(batch, toks, h.samples, h.t_launch, tc, resolve=True, lps=h.logprobs)
 
-    def _process(self, batch, toks, samples, t0: float, tc: float, resolve: bool) -> None:
+    def _process(self, batch, toks, samples, t0: float, tc: float, resolve: bool, lps: dict | None = None) -> None:
         """Post-process one executed step: append (or resolve) sampled tokens, stop checks,
-        streaming deltas, prefix-cache registration, finished requests."""
+        streaming deltas, prefix-cache registration, finished requests. ``lps``: the step's logprob
+        entries by batch item (ModelRunner.collect), stored beside each token."""
         now = time.perf_counter()
         st = self.stats
         st.steps += 1
@@ -627,7 +634,7 @@ class LLMEngine:
         st.batch_sizes[len(batch.items)] += 1
         self.last_step_wall = time.monotonic()
         eos = set(self.arch.eos_token_ids)
-        for (seq, n), tok, smp in zip(batch.items, toks, samples):
+        for i, ((seq, n), tok, smp) in enumerate(zip(batch.items, toks, samples)):
             if not smp:
                 if not seq.is_finished:
                     self.kvm.register_computed(seq)
@@ -637,11 +644,15 @@ class LLMEngine:
                 if seq.is_finished or idx is None:
                     continue  # finished (stop / abort) while this step was in flight: dropped
                 seq.output_ids[idx] = tok
+                if seq.logprobs is not None:
+                    seq.logprobs[idx] = lps.get(i) if lps else None
                 nout = idx + 1
             else:
                 if seq.is_finished:
                     continue
                 seq.output_ids.append(tok)
+                if seq.logprobs is not None:
+                    seq.logprobs.append(lps.get(i) if lps else None)
                 nout = len(seq.output_ids)
             if seq.proc is not None:  # the token is known to the host now: count it (O(1))
                 seq.proc.add_output(tok)
@@ -675,6 +686,8 @@ class LLMEngine:
             if reason is not None:
                 if resolve:  # later in-flight samples of this sequence are discarded
                     del seq.output_ids[nout:]
+                    if seq.logprobs is not None:
+                        del seq.logprobs[nout:]
                     seq.pending.clear()
                 self._finish(seq, reason)
 
@@ -687,6 +700,8 @@ class LLMEngine:
         seq.finish_time = time.perf_counter()
         self._finish_times.append(seq.finish_time)
         if seq.pending:  # abort / error with samples still in flight: drop the placeholders
+            if seq.logprobs is not None:
+                seq.logprobs = [e for t, e in zip(seq.output_ids, seq.logprobs) if t != PENDING]
             seq.output_ids = [t for t in seq.output_ids if t != PENDING]
             seq.pending.clear()
         self._by_id.pop(seq.request_id, None)
@@ -702,6 +717,8 @@ class LLMEngine:
             out = seq.output_ids
             if reason == "stop" and out and out[-1] in self.arch.eos_token_ids:
                 out = out[:-1]
+                if seq.logprobs is not None:  # entries cover the tokens of the returned text
+                    del seq.logprobs[len(out):]
             seq.text = self.tokenizer.decode(out)
         if seq.callback is not None:
             seq.callback("error" if error else "finish", seq, error)
@@ -919,7 +936,7 @@ class LLMEngine:
             "graph_misses_eager": self.runner.graph_misses,
             "pending_captures": len(self.runner.pending_captures),
             "graph_captures": self.runner.captures,
-            "proc_steps": self.runner.proc_steps, "proc_graphs_captured": len(self.runner.proc_graphs),
+            "proc_steps": self.runner.proc_steps, "lp_steps": self.runner.lp_steps, "proc_graphs_captured": len(self.runner.proc_graphs),
             "graph_hit_ratio": round(self.runner.graph_hits / max(1, self.runner.graph_hits + self.runner.graph_misses), 4),
             "max_gpu_step_ms": round(self.runner.max_gpu_ms, 3),
             "max_gpu_step_bucket": list(self.runner.max_gpu_bucket),

@@ -9,6 +9,7 @@ parent touches the GPU) and the API process talks to it over one duplex pipe:
   parent -> child   ("add", rid, prompt, prompt_ids, params, stream) | ("abort", rid)
                     ("call", id, "embed", args) | ("stop",)
   child  -> parent  ("tok", rid, n, delta) | ("fin", rid, kind, fields, error)
+                    (fields of a logprobs request carry its entries and their tokens' bytes)
                     ("snap", snapshot) every 0.25 s | ("ret", id, ok, value)
 
 :class:`EngineProcessClient` exposes the subset of the LLMEngine interface the backends
@@ -38,7 +39,7 @@ class SeqView:
     """What a completion callback may read from a sequence (NativeBackend._result)."""
 
     __slots__ = ("request_id", "text", "output_ids", "prompt_ids", "finish_reason", "first_token_time",
-                 "arrival", "finish_time")
+                 "arrival", "finish_time", "logprobs", "token_bytes")
 
     def __init__(self, request_id: str):
         self.request_id = request_id
@@ -49,12 +50,21 @@ class SeqView:
         self.first_token_time = None
         self.arrival = time.perf_counter()
         self.finish_time = None
+        self.logprobs = None       # the sequence's logprob entries (requests that asked), and the
+        self.token_bytes = None    # core tokenizer's bytes of every token id they name
 
 
-def _fields(seq) -> dict:
-    return {"text": seq.text, "output_ids": list(seq.output_ids), "prompt_len": len(seq.prompt_ids),
-            "finish_reason": seq.finish_reason, "first_token_time": seq.first_token_time, "arrival": seq.arrival,
-            "finish_time": seq.finish_time}
+def _fields(seq, tokenizer=None) -> dict:
+    f = {"text": seq.text, "output_ids": list(seq.output_ids), "prompt_len": len(seq.prompt_ids),
+         "finish_reason": seq.finish_reason, "first_token_time": seq.first_token_time, "arrival": seq.arrival,
+         "finish_time": seq.finish_time}
+    lps = getattr(seq, "logprobs", None)
+    if lps is not None:
+        # the entries cross the pipe with the bytes of their tokens: the core owns the tokenizer
+        from vgate.logprobs import token_ids
+        f["logprobs"] = list(lps)
+        f["token_bytes"] = {t: tokenizer.decode_bytes([t]) for t in token_ids(lps)} if tokenizer is not None else {}
+    return f
 
 
 def _core_main(cfg, conn, snap_period: float = 0.25) -> None:
@@ -86,7 +96,7 @@ def _core_main(cfg, conn, snap_period: float = 0.25) -> None:
             if kind == "token":
                 send(("tok", rid, len(seq.output_ids), payload))
             else:
-                send(("fin", rid, kind, _fields(seq), payload))
+                send(("fin", rid, kind, _fields(seq, eng.tokenizer), payload))
         return cb
 
     stop = threading.Event()
@@ -212,6 +222,7 @@ class EngineProcessClient:
                         sv.output_ids = f["output_ids"]
                         sv.prompt_ids = [0] * f["prompt_len"]
                         sv.finish_reason = f["finish_reason"]
+                        sv.logprobs, sv.token_bytes = f.get("logprobs"), f.get("token_bytes")
                         # perf_counter is CLOCK_MONOTONIC: comparable across processes
                         sv.first_token_time, sv.arrival, sv.finish_time = (f["first_token_time"], f["arrival"],
                                                                            f["finish_time"])
@@ -259,12 +270,14 @@ class EngineProcessClient:
 
     def add_request(self, request_id: str, prompt: str | None = None, params=None, callback=None,
                     stream: bool = False, prompt_ids: list[int] | None = None) -> SeqView:
-        from vgate.runtime.logits_proc import check_request
+        from vgate.runtime.logits_proc import check_logprobs, check_request
         from vgate.runtime.sampling_params import SamplingParams
 
         if params is not None and "vocab_size" in self._snap:
             # refused here as LLMEngine.add_request refuses it (ValueError to the caller)
             check_request(params, self._snap["vocab_size"], 1)
+        if params is not None:
+            check_logprobs(params, self.cfg.tensor_parallel_size)
         sv = SeqView(request_id)
         self._seqs[request_id] = (sv, callback)
         if not self._running:

@@ -46,6 +46,15 @@ def check_request(params, vocab_size: int, tp_size: int = 1) -> None:
         raise ValueError(f"logit_bias holds more than {MAX_BIAS} entries")
 
 
+def check_logprobs(params, tp_size: int = 1) -> None:
+    """Admission check of a logprobs request (same callers as :func:`check_request`)."""
+    if getattr(params, "logprobs", None) is None:
+        return
+    if tp_size > 1:
+        # the TP step ring ships StepMeta only: followers would not know which rows asked
+        raise ValueError("logprobs are not supported with tensor parallelism")
+
+
 class SeqProcState:
     """Unique-token entries of one sequence (prompt tokens, output tokens, biased tokens)."""
 

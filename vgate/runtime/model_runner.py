@@ -21,6 +21,17 @@ unique-token entries) and runs one more kernel between the forward and the sampl
 resolves the row's in-flight token on the device. Processor steps replay their own graphs
 (``proc_graphs``, captured on first use or at idle, never at warm-up); ``graphs`` and every plain
 step are exactly what they are without the feature.
+
+Logprobs: a step in which at least one sampling row belongs to a request with ``logprobs`` set is a
+*logprob step*. After the step's graph replay (or eager forward) the runner enqueues, on the same
+stream, outside any graph and before the step's done event: the upload of the per-row ``k_rows``
+(pinned, double-buffered by ``k``), the two launches of csrc/kernels/logprobs.hip on the step's
+logits (a graph's retained static logits, which the sampler does not write) and ``out_tokens``, and
+one download of the rows' records into pinned ring slot ``k``. No graph table of their own: the
+variants proc x logprob would double both tables to save three launches of host time on opt-in steps,
+so ``graphs``, ``proc_graphs``, ``proc_pending`` and every captured graph are exactly what they are
+without the feature; capturing logprob steps is a later change. The buffers are allocated on the first
+logprob step and never regrown.
 """
 from __future__ import annotations
 
@@ -28,6 +39,7 @@ import bisect
 import logging
 import time
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -57,6 +69,8 @@ class StepHandle:
     bucket: tuple = (0, 0)  # (T, S) graph bucket of the step
     eager: bool = False     # ran without a captured graph (first sight of its bucket)
     timed: bool = False     # a start event was recorded (device time of sampled steps)
+    lp_rows: dict | None = None   # logprob step: batch item -> k of the rows that asked
+    logprobs: dict | None = None  # ... and, once collected: batch item -> (token id, logprob, [(id, logprob)] * k)
 
 
 class ModelRunner:
@@ -91,6 +105,9 @@ class ModelRunner:
         self.proc_pending: dict[tuple[int, int], int] = {}
         self.procmeta: ProcMeta | None = None  # allocated on the first processor step, never regrown
         self.proc_steps = 0
+        # logprob steps: buffers allocated on the first one (None until then), never regrown
+        self.lp = None
+        self.lp_steps = 0
         self.max_model_len = max_model_len
         self.pool = None
         # rounded up to 4 ids: the sampled-id download moves 16-B pieces (ops.host_device_copy)
@@ -273,6 +290,60 @@ class ModelRunner:
             self.procmeta = ProcMeta(self.max_seqs, self.model.arch.vocab_size, self.max_model_len, self.device)
         return self.procmeta
 
+    # ----------------------------------------------------------------- logprobs
+    @staticmethod
+    def _lp_rows(batch: ScheduledBatch, samples: list[bool]) -> dict | None:
+        """Batch item -> k of the rows whose request asked for logprobs and whose sample this step
+        consumes; None: not a logprob step."""
+        rows = None
+        for s, ((seq, _), smp) in enumerate(zip(batch.items, samples)):
+            k = seq.params.logprobs
+            if k is None or not smp:
+                continue
+            if rows is None:
+                rows = {}
+            rows[s] = k
+        return rows
+
+    def _lp_buffers(self):
+        if self.lp is None:
+            n, W = self.out_tokens.numel(), ops.LOGPROB_REC_WORDS  # (n: max_seqs rounded up to 4)
+            k_host = torch.full((2, n), -1, dtype=torch.int32, pin_memory=self.gpu)
+            ring = torch.zeros(2, n, W, dtype=torch.int32, pin_memory=self.gpu)
+            self.lp = SimpleNamespace(
+                k_host=k_host, k_np=k_host.numpy(), ring=ring, ring_np=ring.numpy(),
+                k_dev=torch.full((n,), -1, dtype=torch.int32, device=self.device),
+                rec=torch.zeros(n, W, dtype=torch.int32, device=self.device))
+            if self.gpu:
+                ops.logprob_partials(self.device, n)
+        return self.lp
+
+    def _launch_logprobs(self, logits, rows: dict, ns: int, k: int) -> None:
+        """Enqueue a logprob step's extra work behind the sampler (see the module docstring): k_rows
+        upload, the two launches over rows [0, ns), the records' download into ring slot ``k``."""
+        lp = self._lp_buffers()
+        kh = lp.k_np[k]
+        kh[: (ns + 3) // 4 * 4] = -1
+        for s, kk in rows.items():
+            kh[s] = kk
+        if self.gpu:
+            ops.host_device_copy(lp.k_dev, lp.k_host[k], 4 * ns)
+            ops.logprobs(logits[:ns], self.out_tokens, lp.k_dev, out=lp.rec)
+            ops.host_device_copy(lp.ring[k], lp.rec, 4 * ops.LOGPROB_REC_WORDS * ns)
+        else:
+            ops.logprobs(logits[:ns], self.out_tokens[:ns], lp.k_host[k], out=lp.ring[k])
+        self.lp_steps += 1
+
+    def _lp_entries(self, rows: dict, k: int) -> dict:
+        """The collected records of ring slot ``k`` as batch item -> (token id, logprob, [(id, logprob)])."""
+        r = self.lp.ring_np[k]
+        f = r.view(np.float32)
+        out = {}
+        for s, kk in rows.items():
+            ids, lps = r[s, 2: 2 + 2 * kk: 2].tolist(), f[s, 3: 3 + 2 * kk: 2].tolist()
+            out[s] = (int(r[s, 0]), float(f[s, 1]), [(i, v) for i, v in zip(ids, lps) if i >= 0])
+        return out
+
     # ----------------------------------------------------------------- forward
     def _forward_sample(self, view, proc=None):
         logits = self.model.forward(view, self.kv, self.part_size)
@@ -328,8 +399,8 @@ class ModelRunner:
         sequence id to the previous step's sample slot of its unresolved last token. ``check``:
         TP followers are told to join the consistency exchange after this step (ring mode 4)."""
         if not self.gpu:
-            toks, samples = self._execute_cpu(batch, check)
-            return StepHandle(0, len(batch.items), samples, toks, time.perf_counter())
+            toks, samples, lps = self._execute_cpu(batch, check)
+            return StepHandle(0, len(batch.items), samples, toks, time.perf_counter(), logprobs=lps)
         ns = len(batch.items)
         nt = batch.num_tokens
         T, S = self.bucket_for(nt, ns)
@@ -367,6 +438,7 @@ class ModelRunner:
         if g is not None:
             self.graph_hits += 1
             g.replay()
+            lg = g.vg_out[1]
             if check:
                 self.check_words = self._words(*g.vg_out, nt, ns)
         else:
@@ -382,9 +454,12 @@ class ModelRunner:
             lg = self._forward_sample(view, self.procmeta.view(S) if proc else None)
             if check:
                 self.check_words = self._words(self.model.last_resid, lg, nt, ns)
+        lp_rows = self._lp_rows(batch, samples)
+        if lp_rows is not None:  # logprob step: outside any graph, before the done event
+            self._launch_logprobs(lg, lp_rows, ns, k)
         self.dones[k].record()
         self.host_ms += 1e3 * (time.perf_counter() - t_host)
-        return StepHandle(k, ns, samples, None, t_host, (T, S), eager, timed)
+        return StepHandle(k, ns, samples, None, t_host, (T, S), eager, timed, lp_rows)
 
     def collect(self, h: "StepHandle") -> list[int]:
         """Wait for a launched step and return its sampled ids (one per batch item)."""
@@ -402,6 +477,8 @@ class ModelRunner:
             if len(self.step_gpu_ms) < 65536:
                 self.step_gpu_ms.append(ms)
         toks = self.out_hosts[h.k][: h.ns].tolist()
+        if h.lp_rows is not None:
+            h.logprobs = self._lp_entries(h.lp_rows, h.k)
         self._uncollected[h.k] = False
         self._last_collected = h.k
         return toks
@@ -483,12 +560,14 @@ class ModelRunner:
         view = self.meta.view(nt, ns)
         view.num_tokens, view.num_seqs = nt, ns
         proc = self._fill_proc(batch, samples, ns, 0)
-        logits = self._cpu_sample(view, batch, self.procmeta.view(ns) if proc else None)
+        lp_rows = self._lp_rows(batch, samples)
+        logits = self._cpu_sample(view, batch, self.procmeta.view(ns) if proc else None, lp_rows)
         if check:
             self.check_words = self._words(self.model.last_resid, logits, nt, ns)
-        return self.out_tokens[:ns].tolist(), samples
+        lps = self._lp_entries(lp_rows, 0) if lp_rows is not None else None
+        return self.out_tokens[:ns].tolist(), samples, lps
 
-    def _cpu_sample(self, view, batch, proc=None):
+    def _cpu_sample(self, view, batch, proc=None, lp_rows=None):
         logits = self.model.forward(view, self.kv, self.part_size)
         # the sampler reads a processed copy; the raw logits go back to the caller (TP checksum)
         sampled = ops.process_logits(logits, proc, None) if proc is not None else logits
@@ -498,6 +577,8 @@ class ModelRunner:
             g.manual_seed((seq.seed * 1000003 + len(seq.output_ids)) & 0x7FFFFFFFFFFFFFFF)
             gens.append(g)
         self.out_tokens[: view.S] = ops.ref.sample_ref(sampled, view.temperature, view.top_p, view.top_k, gens)
+        if lp_rows is not None:  # on what the sampler read
+            self._launch_logprobs(sampled, lp_rows, len(batch.items), 0)
         return logits
 
     def warmup(self, token_buckets: list[int] | None = None, seq_buckets: list[int] | None = None) -> float:

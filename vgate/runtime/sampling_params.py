@@ -22,8 +22,15 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logit_bias: dict[int, float] = field(default_factory=dict)
+    # per-token log-probabilities (csrc/kernels/logprobs.hip): None = off, k = 0..20 reports every
+    # generated token's log-probability and the k most likely tokens with theirs, under the softmax at
+    # temperature 1 of the logits as the sampler reads them (after the processors above)
+    logprobs: int | None = None
 
     def __post_init__(self):
+        if self.logprobs is not None:
+            if isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int) or not 0 <= self.logprobs <= 20:
+                raise ValueError("logprobs must be an integer in 0..20")
         if self.temperature < 0:
             raise ValueError("temperature must be >= 0")
         if not (0.0 < self.top_p <= 1.0):

@@ -53,6 +53,9 @@ class Sequence:
     pending_slot: int = -1
     # logits processors: unique-token entries (vgate.runtime.logits_proc.SeqProcState), None = plain
     proc: object = None
+    # logprobs requests (params.logprobs is not None): one entry (token_id, logprob, [(id, logprob), ...])
+    # per output token, aligned with output_ids (None while a token is in flight); None = not asked
+    logprobs: list | None = None
 
     @property
     def all_ids(self) -> list[int]:

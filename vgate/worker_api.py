@@ -4,8 +4,8 @@
 (``{prompts: [str] (>=1), sampling_params: {temperature, top_p, max_tokens}}`` ->
 ``{results: [backend result dicts]}``; 503 before the engine is bound; 500
 ``Inference failed: <Type>``). ``sampling_params`` may also carry the optional sampling controls
-(repetition / presence / frequency penalty, logit_bias, seed, top_k; absent unless the client sent
-them); controls the worker's engine refuses (a logit_bias id outside the vocabulary) answer 400. Async backends are awaited concurrently on the
+(repetition / presence / frequency penalty, logit_bias, seed, top_k, logprobs; absent unless the client
+sent them; results of a ``logprobs`` request carry per-token entries with token strings and bytes); controls the worker's engine refuses (a logit_bias id outside the vocabulary) answer 400. Async backends are awaited concurrently on the
 loop (each prompt is its own engine request, so they batch continuously);
 sync backends run in the executor, serialised by a lock if not concurrency-safe.
 
@@ -107,6 +107,7 @@ class WorkerSamplingParams(BaseModel):
     logit_bias: Optional[dict[int, float]] = None
     seed: Optional[int] = None
     top_k: Optional[int] = None
+    logprobs: Optional[int] = None  # alternatives per token (0..20); results then carry "logprobs"
 
     def extra(self) -> dict:
         """The controls that were sent, as keyword arguments of create_sampling_params."""
@@ -173,6 +174,10 @@ async def _generate(body: GenerateRequest, request: Request):
                 logger.error("Worker inference failed", extra={"extra_data": {
                     "error": str(e), "error_type": type(e).__name__}})
                 raise HTTPException(status_code=500, detail=f"Inference failed: {type(e).__name__}")
+    if sp_in.logprobs is not None:  # the worker owns the tokenizer: results leave with token strings and bytes
+        from vgate.logprobs import annotate_result
+        for r in results:
+            annotate_result(r, backend)
     return {"results": results}
 
 
