@@ -47,7 +47,6 @@ __global__ __launch_bounds__(128) void attn_decode_reduce_kernel(AttnArgs a) {
 // One block per (16-query tile, KV head); wave w < G owns query head h*G + w and
 // its 16 query columns; every wave walks the same KV chunks, V is staged once per
 // block into a double-buffered LDS image (one barrier per chunk).
-template <bool SC1 = false>
 __device__ __forceinline__ void prefill_body(const AttnArgs& a, int tile, int h, char* smem) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nthr = blockDim.x;
@@ -68,12 +67,7 @@ __device__ __forceinline__ void prefill_body(const AttnArgs& a, int tile, int h,
   const int kv_end = min(ctx, ctx - qlen + min(q0 + 16, qlen));
 
   uint4 qf[4];
-  {
-    const bf16_t* qp = a.q + (size_t)(qs + (qok ? qi : 0)) * a.q_stride + (size_t)hq * D_ + 8 * (lane >> 4);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-      qf[kk] = qok ? *reinterpret_cast<const uint4*>(qp + 32 * kk) : make_uint4(0, 0, 0, 0);
-  }
+  load_q_frags(qf, a.q + (size_t)(qs + (qok ? qi : 0)) * a.q_stride + (size_t)hq * D_ + 8 * (lane >> 4), qok);
   const float cscale = a.scale * LOG2E;
   float m = -INFINITY, l = 0.f;
   f32x4 o[8];
@@ -85,11 +79,10 @@ __device__ __forceinline__ void prefill_body(const AttnArgs& a, int tile, int h,
   const size_t head_off = (size_t)h * BS_ * D_;
   const size_t blk_stride = (size_t)a.Hkv * BS_ * D_;
   const int nch = (kv_end + CHUNK - 1) / CHUNK;
-  const int lane64 = threadIdx.x & 63;
-  int btv = 0;  // a 64-entry window of the block table, one entry per lane (see decode_wave)
+  int btv = 0;  // a 64-entry window of the block table, one entry per lane (see decode_block)
   for (int c = 0; c < nch; ++c) {
     const int tb = c * CHUNK;
-    if ((c & 31) == 0) btv = bt[min(2 * c + lane64, a.max_blocks - 1)];
+    if ((c & 31) == 0) btv = bt[min(2 * c + lane, a.max_blocks - 1)];
     const int b0 = __builtin_amdgcn_readlane(btv, (2 * c) & 63);
     const int b1 = (tb + BS_ < kv_end) ? __builtin_amdgcn_readlane(btv, (2 * c + 1) & 63) : b0;
     const bf16_t* vb0 = a.v_cache + (size_t)b0 * blk_stride + head_off;
@@ -112,16 +105,7 @@ __device__ __forceinline__ void prefill_body(const AttnArgs& a, int tile, int h,
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if (!qok) return;
-  const float inv = l > 0.f ? 1.f / l : 0.f;
-  const size_t orow = (size_t)(qs + qi) * a.out_stride + (size_t)hq * D_;
-  const int g = lane >> 4;
-#pragma unroll
-  for (int mt = 0; mt < 8; ++mt) {
-    uint2 pk;
-    pk.x = pack_bf2(o[mt][0] * inv, o[mt][1] * inv);
-    pk.y = pack_bf2(o[mt][2] * inv, o[mt][3] * inv);
-    out_store8<SC1>(a.out, orow + 16 * mt + 4 * g, pk);
-  }
+  store_o_frags(a.out + (size_t)(qs + qi) * a.out_stride + (size_t)hq * D_, o, lane >> 4, l > 0.f ? 1.f / l : 0.f);
 }
 
 // ------------------------------------------------------- flash prefill ----
@@ -131,10 +115,10 @@ __device__ __forceinline__ void prefill_body(const AttnArgs& a, int tile, int h,
 // 64-token chunks, SHARED by the block's waves (GQA: one K/V byte serves G heads x QPB queries),
 // moved by LDS-DMA (global_load_lds_dwordx4: no VGPRs; every wave issues P = ceil(32 / NW) of
 // the chunk's 32 1-KiB pieces, padded with repeats of its own last piece so every wave's vmcnt
-// bookkeeping is the same constant). NST-stage ring: chunk c + NST - 1 is issued at the top of
-// iteration c, so a chunk's DMA has NST - 1 chunks of compute to land — with two stages (one
-// chunk ahead) the kernel ran at the DMA's issue-to-land latency per chunk (~3.4 us, 109 us for
-// Llama-3-8B causal 2048, profiles/r3_flash_prefill.log). One barrier per chunk.
+// bookkeeping is the same constant). FL_NST-stage ring: chunk c + FL_NST - 1 is issued at the top
+// of iteration c, so a chunk's DMA has FL_NST - 1 chunks of compute to land. One barrier per chunk.
+// (Deeper rings, a software-pipelined loop and an eager rescale measured no faster:
+// profiles/r3_flash_prefill.log, profiles/r3_flash_split.log.)
 //   S^T = K Q^T (swapped: softmax statistics lane-local, row reductions by two xor-swaps); K image
 //   16-B chunks XOR-swizzled by row & 15 (conflict-free ds_read_b128 of the A operand);
 //   O^T += V^T P^T with V^T read by ds_read_b64_tr_b16 from the 8-B-chunk-swizzled V image and P^T
@@ -151,7 +135,8 @@ __device__ __forceinline__ void prefill_body(const AttnArgs& a, int tile, int h,
 extern int g_flash_prefill;
 constexpr int FL_KV = 64;
 constexpr int FL_STAGE = 2 * FL_KV * D_ * 2;  // K + V of one chunk (32 KiB)
-constexpr int FL_NST_MAX = 4;                 // ring stages (<= 128 KiB: one block per CU)
+constexpr int FL_NST = 2;                     // ring stages
+constexpr int FL_LDS = FL_NST * FL_STAGE;     // the ring; the block-table window follows it
 // K split hand-off: 16-B words per lane and part for CT column tiles (fp32 o / l: 8 each, then (m, l))
 __host__ __device__ constexpr int FL_SPLIT_WORDS(int ct) { return ct * 8 + 1; }
 
@@ -175,10 +160,9 @@ __device__ __forceinline__ constexpr int vm_imm(int n) {  // s_waitcnt vmcnt(n),
 // dec_seqs > 0: the step's decode rows ride in the same launch — grid rows y >= num_tiles are
 // (sequence, partition) decode blocks (part z == 0 of each KV head), so a prefill or mixed step has
 // ONE attention launch (in a prefill-only step those blocks see no single-token sequence and exit)
-template <int CT, int NW, int FL_NST, bool SWP>
-__global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int lazy, int dec_seqs) {
+template <int CT, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int dec_seqs) {
   constexpr int P = (32 + NW - 1) / NW;  // DMA pieces per wave per chunk
-  constexpr int FL_LDS = FL_NST * FL_STAGE;
   static_assert((FL_NST - 2) * P < 64, "vmcnt immediate");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   TLScope tl_scope(a.tl);
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
   // met in the epilogue; the causal triangle's long tail then costs 1 / nsp of a range per block.
   // Parts past nsp exit at once. Block-uniform, before any barrier.
   const int z = blockIdx.x % zs;
-  const int nsp = SWP ? 1 : min(zs, nch / 2);
+  const int nsp = min(zs, nch / 2);
   const bool split = nsp > 1;
   if (z >= max(nsp, 1)) return;
   const int c0 = split ? nch * z / nsp : 0;
@@ -231,9 +215,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
     const int qi = qw0 + 16 * ct + col;
     const bool ok = qi < qhi;
     lim[ct] = ok ? ctx - qlen + qi + 1 : 0;
-    const bf16_t* qp = a.q + (size_t)(qs + (ok ? qi : 0)) * a.q_stride + (size_t)hq * D_ + 8 * g4;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) qf[ct][kk] = ok ? *reinterpret_cast<const uint4*>(qp + 32 * kk) : make_uint4(0, 0, 0, 0);
+    load_q_frags(qf[ct], a.q + (size_t)(qs + (ok ? qi : 0)) * a.q_stride + (size_t)hq * D_ + 8 * g4, ok);
   }
   const size_t blk_stride = (size_t)a.Hkv * BS_ * D_;
   const size_t head_off = (size_t)h * BS_ * D_;
@@ -298,7 +280,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) o[ct][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const int q = (lane >> 2) & 3, p4 = lane & 3;
+  const int row4 = 4 * g4 + ((lane >> 2) & 3);  // vt_frag's row (pv_update)
   // S^T tiles of chunk c: 4 token tiles x CT column tiles (K from stage c % NST)
   auto qk = [&](int c, f32x4 (&st)[4][CT]) {
     const char* kb = smem + (c % FL_NST) * FL_STAGE;
@@ -316,15 +298,14 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
     }
   };
   // online softmax of chunk c per column tile over its 64 tokens (lane: column col, tokens
-  // 16 tt + 4 g4 + i) -> P^T fragments. SWP: branch-free (mask by select, rescale every chunk),
-  // so the next chunk's QK MFMAs issued before it interleave with this VALU in one basic block
+  // 16 tt + 4 g4 + i) -> P^T fragments
   auto softmax = [&](int c, f32x4 (&st)[4][CT], bf16x8 (&pb)[CT][2]) {
     const bool masked = c >= nfull;  // block-uniform
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      if (SWP || masked) {
+      if (masked) {
         // token t = c 64 + 16 tt + 4 g4 + i is masked when t >= lim: i.e. 16 tt + i >= lim - c 64 - 4 g4
-        const int rel = (SWP && !masked ? 0x3fffffff : lim[ct]) - c * FL_KV - 4 * g4;
+        const int rel = lim[ct] - c * FL_KV - 4 * g4;
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
@@ -339,7 +320,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
       cmax = fmax_(cmax, xor16(cmax));
       cmax = fmax_(cmax, xor32(cmax));
       const float mn = fmaxf(m[ct], cmax * cscale);
-      if (SWP || !lazy || __any(mn > m[ct])) {  // wave-uniform: rescale only when a running max moved
+      if (__any(mn > m[ct])) {  // lazy rescale (wave-uniform): only when a running max moved
         const float alpha = __builtin_amdgcn_exp2f(m[ct] - (mn == -INFINITY ? 0.f : mn));
         l[ct] *= alpha;
 #pragma unroll
@@ -368,60 +349,27 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
       const bf16_t* vh = vb + half * (32 * D_);
 #pragma unroll
       for (int mt = 0; mt < 8; ++mt) {
-        const int cc = 16 * mt + 4 * p4;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(vh + v_lds_off(4 * g4 + q, cc)));
-        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(vh + v_lds_off(16 + 4 * g4 + q, cc)));
-        bf16x8 av;
-        av[0] = lo[0]; av[1] = lo[1]; av[2] = lo[2]; av[3] = lo[3];
-        av[4] = hi[0]; av[5] = hi[1]; av[6] = hi[2]; av[7] = hi[3];
+        const bf16x8 av = vt_frag(vh, row4, 16 * mt + 4 * (lane & 3));
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) o[ct][mt] = mfma16(av, pb[ct][half], o[ct][mt]);
       }
     }
   };
-  if constexpr (!SWP) {
-    if (c1 > c0) {
+  if (c1 > c0) {
 #pragma unroll
-      for (int c = 0; c < FL_NST - 1; ++c) issue(c0 + c);
-    }
-    __builtin_amdgcn_s_waitcnt(vm_imm((FL_NST - 2) * P));  // chunk c0 landed (this wave's pieces)
-    __builtin_amdgcn_s_barrier();                          // everyone's
-    for (int c = c0; c < c1; ++c) {
-      issue(c + FL_NST - 1);  // into the stage every wave finished reading last iteration
-      f32x4 st[4][CT];
-      bf16x8 pb[CT][2];
-      qk(c, st);
-      softmax(c, st, pb);
-      pv(c, pb);
-      __builtin_amdgcn_s_waitcnt(vm_imm((FL_NST - 2) * P));  // this wave's pieces of chunk c + 1 landed
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // everyone's; stage c % NST free
-    }
-  } else {
-    // software-pipelined: iteration c computes S of chunk c + 1 (MFMA) beside the softmax of chunk c
-    // (VALU), then P V of chunk c. Live stages: c (V), c + 1 (K), c + 2 (landing), c + 3 (issued)
-    static_assert(FL_NST >= 4, "the pipelined loop keeps four chunks resident");
-    if (nch > 0) {
-#pragma unroll
-      for (int c = 0; c < FL_NST - 1; ++c) issue(c);
-    }
-    __builtin_amdgcn_s_waitcnt(vm_imm((FL_NST - 3) * P));  // chunks 0 and 1 landed (this wave's pieces)
-    __builtin_amdgcn_s_barrier();                          // everyone's
-    f32x4 sc[4][CT];
-    if (nch > 0) qk(0, sc);
-    for (int c = 0; c < nch; ++c) {
-      issue(c + FL_NST - 1);  // into stage (c - 1) % NST: every wave finished its P V in iteration c - 1
-      f32x4 sn[4][CT];
-      bf16x8 pb[CT][2];
-      qk(c + 1, sn);  // past the last chunk: the re-read last chunk, discarded
-      softmax(c, sc, pb);
-      pv(c, pb);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) sc[tt][ct] = sn[tt][ct];
-      __builtin_amdgcn_s_waitcnt(vm_imm((FL_NST - 3) * P));  // this wave's pieces of chunk c + 2 landed
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // everyone's; stage c % NST free
-    }
+    for (int c = 0; c < FL_NST - 1; ++c) issue(c0 + c);
+  }
+  __builtin_amdgcn_s_waitcnt(vm_imm((FL_NST - 2) * P));  // chunk c0 landed (this wave's pieces)
+  __builtin_amdgcn_s_barrier();                          // everyone's
+  for (int c = c0; c < c1; ++c) {
+    issue(c + FL_NST - 1);  // into the stage every wave finished reading last iteration
+    f32x4 st[4][CT];
+    bf16x8 pb[CT][2];
+    qk(c, st);
+    softmax(c, st, pb);
+    pv(c, pb);
+    __builtin_amdgcn_s_waitcnt(vm_imm((FL_NST - 2) * P));  // this wave's pieces of chunk c + 1 landed
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // everyone's; stage c % NST free
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the look-ahead DMAs drained before the block exits
   if (split) {
@@ -524,15 +472,7 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
         for (int mt = 0; mt < 8; ++mt) acc[mt] += v[mt] * wp;
       }
       const int qi = qw0 + 16 * ct + col;
-      if (qi >= qhi) continue;
-      const size_t orow = (size_t)(qs + qi) * a.out_stride + (size_t)hq * D_;
-#pragma unroll
-      for (int mt = 0; mt < 8; ++mt) {
-        uint2 pk;
-        pk.x = pack_bf2(acc[mt][0], acc[mt][1]);
-        pk.y = pack_bf2(acc[mt][2], acc[mt][3]);
-        *reinterpret_cast<uint2*>(a.out + orow + 16 * mt + 4 * g4) = pk;
-      }
+      if (qi < qhi) store_o_frags(a.out + (size_t)(qs + qi) * a.out_stride + (size_t)hq * D_, acc, g4);
     }
     return;
   }
@@ -542,23 +482,17 @@ __global__ __launch_bounds__(64 * NW) void attn_flash_kernel(AttnArgs a, int laz
     ll += xor16(ll);
     ll += xor32(ll);
     const int qi = qw0 + 16 * ct + col;
-    if (qi >= qhi) continue;
-    const float inv = ll > 0.f ? 1.f / ll : 0.f;
-    const size_t orow = (size_t)(qs + qi) * a.out_stride + (size_t)hq * D_;
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-      uint2 pk;
-      pk.x = pack_bf2(o[ct][mt][0] * inv, o[ct][mt][1] * inv);
-      pk.y = pack_bf2(o[ct][mt][2] * inv, o[ct][mt][3] * inv);
-      *reinterpret_cast<uint2*>(a.out + orow + 16 * mt + 4 * g4) = pk;
-    }
+    if (qi < qhi)
+      store_o_frags(a.out + (size_t)(qs + qi) * a.out_stride + (size_t)hq * D_, o[ct], g4, ll > 0.f ? 1.f / ll : 0.f);
   }
 }
 
 // flash configuration for a head group of G (ct = 0: not supported): waves NW = 8 when G | 8
 // (G query groups of 8 / G), 6 for G = 3, 6; two 16-query column tiles per wave for G <= 4
 // (Llama: 64-query blocks), one above (16-query blocks keep >= one block per CU at 2k tokens for
-// the 1-2 KV-head layouts; two there were slower at every length, profiles/r3_flash_split.log)
+// the 1-2 KV-head layouts; two there were slower at every length, profiles/r3_flash_split.log).
+// The head-group rule is restated by ops.flash_lead (vgate/ops/__init__.py, which must work without
+// this module) and by tests/test_attn_probe_gpu.py _has_flash: change the three together.
 struct FlashCfg { int ct, nw; };
 static FlashCfg flash_cfg(const AttnArgs& a) {
   if (a.D != D_ || a.BS != BS_ || a.Hkv <= 0 || a.Hq % a.Hkv) return {0, 0};
@@ -603,79 +537,53 @@ static int attn_waves(const AttnArgs& a) {
 int g_flash_prefill = -1;  // -1: VGATE_FLASH_PREFILL (default on); 0 / 1: set_flash_prefill (tests)
 void set_flash_prefill(int on) { g_flash_prefill = on; }
 
+// K split of the long causal ranges (zs parts per KV head, adjacent in grid.x) when the
+// workspace holds every wave's partials: 2 parts while the step's working blocks fill less
+// than two waves of the chip's block slots (CT = 2 blocks hold a CU alone, CT = 1 two), 4
+// while 4 parts per block still fit in one wave (profiles/r3_flash_split.log: 4 parts won
+// only there: Llama-3-70B TP=8 2048 39.8 -> 31.9 us, lost at Qwen 2048 46 -> 50, Llama-8B
+// 1024 35 -> 45); none once the blocks alone fill two waves (they balance the triangle)
+static int flash_split_parts(const AttnArgs& a, FlashCfg fc, int tiles) {
+  if (a.fl_ws == nullptr || a.fl_tickets == nullptr) return 1;
+  const int qpb = 16 * fc.ct * (fc.nw / (a.Hq / a.Hkv));
+  const size_t leaders = (size_t)tiles * 16 / qpb + (size_t)a.S + 1;
+  const size_t slots = leaders * a.Hkv * fc.nw;
+  const size_t blocks = (size_t)tiles * 16 / qpb * a.Hkv;
+  const size_t cap = (size_t)cu_count(1) * (fc.ct == 2 ? 1 : 2);
+  int zs = 1;
+  if (blocks < 2 * cap) zs = 2;
+  if (blocks * 4 <= cap) zs = 4;
+  if (slots > 32768 || slots * zs * FL_SPLIT_WORDS(fc.ct) * 1024 > a.fl_ws_bytes) zs = 1;
+  return zs;
+}
+
 void launch_attention(const AttnArgs& a, int dec_seqs, hipStream_t st) {
-  int tiles = a.num_tiles > 0 ? a.num_tiles : 0;
-  // prefill tiles on the flash kernel (its own launch; a decode-only graph bucket carries no tile
-  // list, StepMeta.view), the unified kernel keeps the decode rows
-  const FlashCfg fc = tiles > 0 && flash_enabled() ? flash_cfg(a) : FlashCfg{0, 0};
-  if (fc.ct > 0) {
-    AttnArgs f = a;
-    f.num_tiles = tiles;
-    // the decode rows join this launch (grid rows past the tiles): no second attention launch
-    const int dec_rows = dec_seqs > 0 ? dec_seqs * a.num_parts : 0;
-    // a 2-stage K/V ring with the lazy rescale (4 stages and eager rescale measured no faster:
-    // profiles/r3_flash_split.log)
-    constexpr int lazy = 1;
-    const size_t lds = (size_t)2 * FL_STAGE + (size_t)a.max_blocks * 4;
-    // K split of the long causal ranges (zs parts per KV head, adjacent in grid.x) when the
-    // workspace holds every wave's partials: 2 parts while the step's working blocks fill less
-    // than two waves of the chip's block slots (CT = 2 blocks hold a CU alone, CT = 1 two), 4
-    // while 4 parts per block still fit in one wave (profiles/r3_flash_split.log: 4 parts won
-    // only there: Llama-3-70B TP=8 2048 39.8 -> 31.9 us, lost at Qwen 2048 46 -> 50, Llama-8B
-    // 1024 35 -> 45); none once the blocks alone fill two waves (they balance the triangle)
-    int zs = 1;
-    if (f.fl_ws != nullptr && f.fl_tickets != nullptr) {
-      const int qpb = 16 * fc.ct * (fc.nw / (a.Hq / a.Hkv));
-      const size_t leaders = (size_t)tiles * 16 / qpb + (size_t)a.S + 1;
-      const size_t slots = leaders * a.Hkv * fc.nw;
-      const size_t blocks = (size_t)tiles * 16 / qpb * a.Hkv;
-      const size_t cap = (size_t)cu_count(1) * (fc.ct == 2 ? 1 : 2);
-      if (blocks < 2 * cap) zs = 2;
-      if (blocks * 4 <= cap) zs = 4;
-      if (slots > 32768 || slots * zs * FL_SPLIT_WORDS(fc.ct) * 1024 > f.fl_ws_bytes) zs = 1;
-    }
-    const dim3 grid(a.Hkv * zs, tiles + dec_rows, 1), block(64 * fc.nw);
-    f.tl = tl_take("attn_flash", (tiles + dec_rows) * a.Hkv * zs);
-    const size_t lds_all = std::max(lds, (size_t)attn_lds_bytes(fc.nw));
-#define VG_FL(CT_, NW_) hipLaunchKernelGGL((attn_flash_kernel<CT_, NW_, 2, false>), grid, block, lds_all, st, f, lazy, dec_seqs)
-    if (fc.nw == 8) {
-      if (fc.ct == 2) VG_FL(2, 8); else VG_FL(1, 8);
-    } else {
-      if (fc.ct == 2) VG_FL(2, 6); else VG_FL(1, 6);
-    }
-#undef VG_FL
-    if (dec_seqs > 0 && a.num_parts > 1 && a.tickets == nullptr) {
-      AttnArgs b = a;
-      b.tl = tl_take("attn_reduce", dec_seqs * a.Hq);
-      hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(dec_seqs, a.Hq), dim3(128), 0, st, b);
-    }
-    return;
-  }
-  const int nw = attn_waves(a);
+  const int tiles = a.num_tiles > 0 ? a.num_tiles : 0;
   const int dec_blocks = dec_seqs > 0 ? dec_seqs * a.num_parts : 0;
-  const int nx = dec_blocks + tiles;
-  if (nx <= 0) return;
+  if (tiles + dec_blocks <= 0) return;
   AttnArgs b = a;
   b.num_tiles = tiles;
-  b.tl = tl_take("attention", nx * a.Hkv);
-  if (nw <= 8)
-    hipLaunchKernelGGL(attn_kernel<512>, dim3(nx, a.Hkv, 1), dim3(64 * nw), attn_lds_bytes(nw), st, b, dec_seqs, dec_blocks);
-  else
-    hipLaunchKernelGGL(attn_kernel<1024>, dim3(nx, a.Hkv, 1), dim3(64 * nw), attn_lds_bytes(nw), st, b, dec_seqs, dec_blocks);
-  if (dec_seqs > 0 && a.num_parts > 1 && a.tickets == nullptr) {
+  // prefill tiles on the flash kernel when it takes the head layout (a decode-only graph bucket
+  // carries no tile list, StepMeta.view); either way the decode rows ride in the same launch
+  const FlashCfg fc = tiles > 0 && flash_enabled() ? flash_cfg(a) : FlashCfg{0, 0};
+  if (fc.ct > 0) {
+    const int zs = flash_split_parts(a, fc, tiles);
+    const size_t lds = std::max((size_t)FL_LDS + (size_t)a.max_blocks * 4, (size_t)attn_lds_bytes(fc.nw));
+    b.tl = tl_take("attn_flash", (tiles + dec_blocks) * a.Hkv * zs);
+    const auto kern = fc.nw == 8 ? (fc.ct == 2 ? attn_flash_kernel<2, 8> : attn_flash_kernel<1, 8>)
+                                 : (fc.ct == 2 ? attn_flash_kernel<2, 6> : attn_flash_kernel<1, 6>);
+    hipLaunchKernelGGL(kern, dim3(a.Hkv * zs, tiles + dec_blocks, 1), dim3(64 * fc.nw), lds, st, b, dec_seqs);
+  } else {
+    const int nw = attn_waves(a);
+    b.tl = tl_take("attention", (tiles + dec_blocks) * a.Hkv);
+    const auto kern = nw <= 8 ? attn_kernel<512> : attn_kernel<1024>;
+    hipLaunchKernelGGL(kern, dim3(dec_blocks + tiles, a.Hkv, 1), dim3(64 * nw), attn_lds_bytes(nw), st, b, dec_seqs,
+                       dec_blocks);
+  }
+  if (dec_seqs > 0 && a.num_parts > 1 && a.tickets == nullptr) {  // the partitions' separate reduce launch
     b.tl = tl_take("attn_reduce", dec_seqs * a.Hq);
     hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(dec_seqs, a.Hq), dim3(128), 0, st, b);
   }
-}
-
-void launch_attn_decode(const AttnArgs& a, hipStream_t st) {
-  AttnArgs b = a;
-  b.num_tiles = 0;
-  launch_attention(b, a.S, st);
-}
-
-void launch_attn_prefill(const AttnArgs& a, hipStream_t st) {
-  launch_attention(a, 0, st);
 }
 
 }  // namespace vgate

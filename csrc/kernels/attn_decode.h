@@ -47,24 +47,45 @@ __device__ __forceinline__ void store_v_lds(bf16_t* lds, const uint4 (&vr)[8], i
   }
 }
 
+// V^T A-operand fragment of P V for output columns c .. c + 3: the two transposed 4-row x 16-col
+// gathers (ds_read_b64_tr_b16) at rows row4 and 16 + row4 give the k-order {4g..4g+3, 16+4g..16+4g+3}
+__device__ __forceinline__ bf16x8 vt_frag(const bf16_t* lds, int row4, int c) {
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds + v_lds_off(row4, c)));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds + v_lds_off(16 + row4, c)));
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
 // O^T[16mt + ..][col] += V^T(chunk) . P^T ; pb = P^T fragment (bf16x8)
 __device__ __forceinline__ void pv_update(f32x4 (&o)[8], const bf16_t* lds, const bf16x8& pb,
                                           int lane) {
-  const int g = lane >> 4;
-  const int q = (lane >> 2) & 3;
-  const int p = lane & 3;
+  const int row4 = 4 * (lane >> 4) + ((lane >> 2) & 3);
+#pragma unroll
+  for (int mt = 0; mt < 8; ++mt) o[mt] = mfma16(vt_frag(lds, row4, 16 * mt + 4 * (lane & 3)), pb, o[mt]);
+}
+
+// Q fragments (B operand of S^T = K Q^T) of one query column: four 16-B k-slices from qp (the
+// column's row + 8 (lane >> 4)), zero for a column out of range (qp is then never read)
+__device__ __forceinline__ void load_q_frags(uint4 (&qf)[4], const bf16_t* qp, bool ok) {
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) qf[kk] = ok ? *reinterpret_cast<const uint4*>(qp + 32 * kk) : make_uint4(0, 0, 0, 0);
+}
+
+// Output epilogue of one query column: the lane's O^T values (d = 16 mt + 4 g + i) as bf16, one 8-B
+// store per mt. orow: the column's output row. Scaled form: o * scale, then the pack.
+__device__ __forceinline__ void store_o_frags(bf16_t* orow, const f32x4 (&v)[8], int g) {
 #pragma unroll
   for (int mt = 0; mt < 8; ++mt) {
-    const int c = 16 * mt + 4 * p;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-        (lds_bf16x4*)(lds + v_lds_off(4 * g + q, c)));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-        (lds_bf16x4*)(lds + v_lds_off(16 + 4 * g + q, c)));
-    bf16x8 a;
-    a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
-    a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
-    o[mt] = mfma16(a, pb, o[mt]);
+    uint2 pk;
+    pk.x = pack_bf2(v[mt][0], v[mt][1]);
+    pk.y = pack_bf2(v[mt][2], v[mt][3]);
+    *reinterpret_cast<uint2*>(orow + 16 * mt + 4 * g) = pk;
   }
+}
+__device__ __forceinline__ void store_o_frags(bf16_t* orow, const f32x4 (&o)[8], int g, float scale) {
+  f32x4 v[8];
+#pragma unroll
+  for (int mt = 0; mt < 8; ++mt) v[mt] = o[mt] * scale;
+  store_o_frags(orow, v, g);
 }
 
 __device__ __forceinline__ bf16x8 pack_p(const f32x4& s0, const f32x4& s1) {
@@ -127,8 +148,7 @@ __device__ __forceinline__ bf16x8 softmax_step(f32x4& s0, f32x4& s1, float& m, f
 
 // LDS: max(decode: one V image (then o partial) per wave + (m, l) + flag, prefill double buffer)
 __host__ __device__ constexpr int attn_lds_bytes(int nw) {
-  return nw * CHUNK * D_ * 2 + nw * 32 * 4 + 16 > 2 * CHUNK * D_ * 2 ? nw * CHUNK * D_ * 2 + nw * 32 * 4 + 16
-                                                                     : 2 * CHUNK * D_ * 2;
+  return std::max(nw * CHUNK * D_ * 2 + nw * 32 * 4 + 16, 2 * CHUNK * D_ * 2);
 }
 
 // ---------------------------------------------------------------- decode ----
@@ -162,26 +182,6 @@ __device__ __forceinline__ void load_k_regs(uint4 (&kf)[8], const bf16_t* kb0, c
 // 16 cols x 128 d = the same 8 KiB) | [nw][16][2] (m, l) | flag
 __host__ __device__ constexpr int dec_ml_off(int nw) { return nw * CHUNK * D_ * 2; }
 
-// Output stores. SC1: write-through (device-coherent) stores, for a consumer that reads the
-// result inside the same launch (a consumer in the same launch loads it with sc1 loads)
-template <bool SC1>
-__device__ __forceinline__ void out_store16(bf16_t* base, size_t elem, uint4 v) {
-  if constexpr (SC1) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f32x4, v), rsrc_of(base), (uint32_t)(elem * 2), 0, 16);
-  } else {
-    *reinterpret_cast<uint4*>(base + elem) = v;
-  }
-}
-template <bool SC1>
-__device__ __forceinline__ void out_store8(bf16_t* base, size_t elem, uint2 v) {
-  if constexpr (SC1) {
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(u32x2{v.x, v.y}, rsrc_of(base), (uint32_t)(elem * 2), 0, 16);
-  } else {
-    *reinterpret_cast<uint2*>(base + elem) = v;
-  }
-}
-
 // Fused QKV projection + decode attention (qkv_attn.hip): the handed-off values travel as data-tagged
 // granules, 8 B = {a bf16 pair, tag} with tag = position + 1 of the row, written by the GEMM epilogue
 // (16-B write-through stores of two granules) and polled by the consumer with 16-B sc1 loads until
@@ -201,7 +201,7 @@ __device__ __forceinline__ bool qa_get8(const QaSync& q, uint32_t pair, uint32_t
 // once; the query fragments and the new token's K / V row (position ctx - 1) come from the producer
 // blocks' granules (qa_get8), never through a plain load of the cache row the producer is writing
 // (the prefetched chunk reads the neighbouring row in its place and is patched).
-template <bool SC1 = false, bool FUSED = false>
+template <bool FUSED = false>
 __device__ __forceinline__ void decode_block(const AttnArgs& a, int s, int h, int part, char* smem,
                                              const QaSync* qs = nullptr) {
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -224,9 +224,7 @@ __device__ __forceinline__ void decode_block(const AttnArgs& a, int s, int h, in
     // a sequence that is not decode work (the block exits below) must not steer this early load: an
     // empty sequence at the end of a step (the padding of a graph bucket) has qbeg = the row BEHIND q
     const int qrow = qend - qbeg == 1 ? qbeg : 0;
-    const bf16_t* qp = a.q + (size_t)qrow * a.q_stride + (size_t)(h * G + (cok ? col : 0)) * D_ + 8 * (lane >> 4);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) qf[kk] = cok ? *reinterpret_cast<const uint4*>(qp + 32 * kk) : make_uint4(0, 0, 0, 0);
+    load_q_frags(qf, a.q + (size_t)qrow * a.q_stride + (size_t)(h * G + (cok ? col : 0)) * D_ + 8 * (lane >> 4), cok);
   }
   if (ctx <= 0 || pstart >= ctx || qend - qbeg != 1) return;  // block-uniform
   ATTN_STAMP(1);
@@ -495,7 +493,7 @@ __device__ __forceinline__ void decode_block(const AttnArgs& a, int s, int h, in
       pk.y = pack_bf2(acc[2] * inv, acc[3] * inv);
       pk.z = pack_bf2(acc[4] * inv, acc[5] * inv);
       pk.w = pack_bf2(acc[6] * inv, acc[7] * inv);
-      out_store16<SC1>(a.out, (size_t)qbeg * a.out_stride + (size_t)hq * D_ + d0, pk);
+      *reinterpret_cast<uint4*>(a.out + (size_t)qbeg * a.out_stride + (size_t)hq * D_ + d0) = pk;
     }
     ATTN_STAMP(3);
     return;
@@ -547,7 +545,7 @@ __device__ __forceinline__ void decode_block(const AttnArgs& a, int s, int h, in
     uint2 pk;
     pk.x = pack_bf2(r[0] * iv, r[1] * iv);
     pk.y = pack_bf2(r[2] * iv, r[3] * iv);
-    out_store8<SC1>(a.out, (size_t)qbeg * a.out_stride + (size_t)hh * D_ + dd, pk);
+    *reinterpret_cast<uint2*>(a.out + (size_t)qbeg * a.out_stride + (size_t)hh * D_ + dd) = pk;
   }
 }
 

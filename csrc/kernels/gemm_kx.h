@@ -314,7 +314,7 @@ __global__ __launch_bounds__(512) void kx_qa_kernel(GemmParams p, AttnArgs a, Qa
   }
   TLScope tl_scope(p.dbg_ts);
   const int r = (int)blockIdx.x - q.nprod;  // (KV head, partition, sequence), sequence fastest
-  decode_block<false, true>(a, r % a.S, r / (a.S * a.num_parts), (r / a.S) % a.num_parts, smem, &q);
+  decode_block<true>(a, r % a.S, r / (a.S * a.num_parts), (r / a.S) % a.num_parts, smem, &q);
 }
 
 template <bool Q4, int XP, int NORM>

@@ -235,9 +235,9 @@ struct AttnArgs {
   // profiling only: phase timestamps (s_memtime) of block (0,0,0) wave 0, or null
   unsigned long long* dbg_ts;
   unsigned long long* tl;  // launch timeline slot (set by the launcher), or null
-  // flash prefill K split (attention.hip attn_flash_kernel, two blocks per KV head): the two halves of a long
-  // causal range meet through fp32 partials + (m, l) in fl_ws and a zeroed, self-resetting
-  // ticket + ready word per (leader, KV head, wave) (fl_tickets: 65536 words); null -> no split
+  // flash prefill K split (attention.hip attn_flash_kernel; 1, 2 or 4 parts per KV head, chosen by
+  // flash_split_parts): the parts of a long causal range meet through fp32 partials + (m, l) in fl_ws and a
+  // zeroed, self-resetting ticket + ready word per (leader, KV head, wave) (fl_tickets: 65536 words); null -> no split
   float* fl_ws = nullptr;
   size_t fl_ws_bytes = 0;
   uint32_t* fl_tickets = nullptr;
@@ -255,10 +255,9 @@ struct QaSync {
   int nprod;
   uint32_t* fault;
 };
-void launch_attn_decode(const AttnArgs& a, hipStream_t st);
-void launch_attn_prefill(const AttnArgs& a, hipStream_t st);
 // One launch for a mixed step: decode blocks for sequences [0, dec_seqs) (only those
-// with a single query token do work) + prefill tiles (tile_seq < 0 = padding).
+// with a single query token do work) + prefill tiles (tile_seq < 0 = padding). Decode only:
+// num_tiles = 0, dec_seqs = S; prefill only: dec_seqs = 0.
 void launch_attention(const AttnArgs& a, int dec_seqs, hipStream_t st);
 
 

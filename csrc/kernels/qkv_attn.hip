@@ -7,7 +7,7 @@
 // written by earlier launches. So the attention blocks ride behind the GEMM blocks of the projection
 // launch (block ids [nprod, nprod + ncons)): each requests its context metadata and the first K / V
 // chunk of every wave at launch, while the GEMM streams its weights on other CUs, then waits for the
-// GEMM blocks' arrivals and loads only q and the new row (attn_decode.h decode_block<.., FUSED>).
+// GEMM blocks' arrivals and loads only q and the new row (attn_decode.h decode_block<FUSED>).
 //
 // Hand-off (MI355X_MICROARCH.md handoff-1to1, R2 granules): the producer epilogue writes q and the new
 // K / V rows a second time as data-tagged granules {bf16 pair, position + 1} (16-B write-through
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(GemmParams p, AttnArgs a,
   // consumer r = (KV head, partition, sequence), sequence fastest (as attn_kernel's decode blocks)
   const int r = (int)blockIdx.x - q.nprod;
   const int S = a.S, P = a.num_parts;
-  decode_block<false, true>(a, r % S, r / (S * P), (r / S) % P, smem, &q);
+  decode_block<true>(a, r % S, r / (S * P), (r / S) % P, smem, &q);
 }
 
 template <int NORM>

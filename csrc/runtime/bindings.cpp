@@ -43,10 +43,71 @@ T* opt_ptr(const c10::optional<Tensor>& t, c10::ScalarType dt, const char* name)
   return reinterpret_cast<T*>(t->data_ptr());
 }
 
+// Argument checks shared by the attention entry points (attn_decode, attn_prefill, attention and
+// gemm's fused attention): attn_common first (it sets S, Hq, Hkv, max_blocks), then the attn_set_*
+// of the buffers the entry point takes.
 vgate::AttnArgs attn_common(const Tensor& q, int64_t q_stride, const Tensor& k_cache,
                             const Tensor& v_cache, const Tensor& block_tables,
                             const Tensor& context_lens, Tensor& out, int64_t Hq, int64_t Hkv,
-                            double scale);
+                            double scale) {
+  CHECK_DEV(q); CHECK_DEV(k_cache); CHECK_DEV(v_cache); CHECK_DEV(block_tables);
+  CHECK_DEV(context_lens); CHECK_DEV(out);
+  CHECK_DT(q, torch::kBFloat16); CHECK_DT(out, torch::kBFloat16);
+  CHECK_DT(block_tables, torch::kInt32); CHECK_DT(context_lens, torch::kInt32);
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16 && k_cache.size(3) == 128,
+              "attention: cache must be [nblk, Hkv, 16, 128]");
+  TORCH_CHECK(Hq % Hkv == 0 && Hq / Hkv <= 16, "attention: GQA group must be <= 16");
+  TORCH_CHECK(block_tables.is_contiguous(), "attention: block_tables contiguous");
+  vgate::AttnArgs a{};
+  a.q = bf16p(q); a.q_stride = (int)q_stride;
+  a.k_cache = bf16p(k_cache); a.v_cache = bf16p(v_cache);
+  a.block_tables = reinterpret_cast<const int32_t*>(block_tables.data_ptr());
+  a.max_blocks = (int)block_tables.size(1);
+  a.context_lens = reinterpret_cast<const int32_t*>(context_lens.data_ptr());
+  a.out = bf16p_mut(out); a.out_stride = (int)(Hq * 128);
+  TORCH_CHECK(out.is_contiguous(), "attention: out contiguous");
+  a.S = (int)context_lens.numel();
+  a.Hq = (int)Hq; a.Hkv = (int)Hkv; a.D = 128; a.BS = 16;
+  a.scale = (float)scale;
+  return a;
+}
+
+// decode split-K partials: part_o [>= S, Hq, P, 128], part_ml [S, Hq, P, 2], P partitions of part_size tokens
+static void attn_set_parts(vgate::AttnArgs& a, const Tensor& part_o, const Tensor& part_ml, int64_t part_size) {
+  CHECK_DT(part_o, torch::kFloat32); CHECK_DT(part_ml, torch::kFloat32);
+  TORCH_CHECK(part_size % 32 == 0 && part_size <= 1024, "attention: part_size must be a multiple of 32, <= 1024");
+  TORCH_CHECK(part_o.dim() == 4 && part_o.size(0) >= a.S && part_o.size(1) == a.Hq && part_o.size(3) == 128,
+              "attention: part_o must be [S, Hq, P, 128]");
+  a.num_parts = (int)part_o.size(2);
+  a.part_size = (int)part_size;
+  TORCH_CHECK(part_ml.numel() >= (int64_t)a.S * a.Hq * a.num_parts * 2, "attention: part_ml must be [S, Hq, P, 2]");
+  TORCH_CHECK((int64_t)a.num_parts * part_size >= (int64_t)a.max_blocks * 16,
+              "attention: partitions do not cover max context");
+  a.part_o = reinterpret_cast<float*>(part_o.data_ptr());
+  a.part_ml = reinterpret_cast<float*>(part_ml.data_ptr());
+}
+
+static void attn_set_queries(vgate::AttnArgs& a, const c10::optional<Tensor>& query_start) {  // none: decode rows
+  a.query_start = opt_ptr<const int32_t>(query_start, torch::kInt32, "query_start");
+  TORCH_CHECK(!a.query_start || query_start->numel() >= a.S + 1, "attention: query_start needs S+1 entries");
+}
+
+static void attn_set_tiles(vgate::AttnArgs& a, const Tensor& tile_seq, const Tensor& tile_q0) {
+  CHECK_DT(tile_seq, torch::kInt32); CHECK_DT(tile_q0, torch::kInt32);
+  a.tile_seq = reinterpret_cast<const int32_t*>(tile_seq.data_ptr());
+  a.tile_q0 = reinterpret_cast<const int32_t*>(tile_q0.data_ptr());
+  a.num_tiles = (int)tile_seq.numel();
+}
+
+static void attn_set_tickets(vgate::AttnArgs& a, const c10::optional<Tensor>& tickets) {
+  a.tickets = reinterpret_cast<uint32_t*>(opt_ptr<int32_t>(tickets, torch::kInt32, "tickets"));
+  TORCH_CHECK(!a.tickets || tickets->numel() >= (int64_t)a.S * a.Hkv, "attention: tickets need S*Hkv zeroed int32");
+}
+
+static void attn_set_dbg(vgate::AttnArgs& a, const c10::optional<Tensor>& dbg_ts) {  // profiling: phase stamps
+  a.dbg_ts = reinterpret_cast<unsigned long long*>(opt_ptr<int64_t>(dbg_ts, torch::kInt64, "dbg_ts"));
+  TORCH_CHECK(!a.dbg_ts || dbg_ts->numel() >= 16, "attention: dbg_ts needs 16 int64");
+}
 
 // out = epilogue(prologue(x) @ W^T); W fragment-packed [N/16, K/32, 64, 8] bf16, or AWQ
 // int4 [N/16, K/128, 64, 4] int32 with scales/zeros. ws = int32 workspace: [0, 65536)
@@ -195,29 +256,14 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
     Tensor fo = *fa_out;
     fa = attn_common(out, out.stride(0), *k_cache, *v_cache, *fa_block_tables, *fa_context_lens, fo, hq, hkv,
                      fa_scale);
-    TORCH_CHECK(fa_part_size % 32 == 0 && fa_part_size <= 1024, "fused attention: part_size");
-    CHECK_DT(*fa_part_o, torch::kFloat32); CHECK_DT(*fa_part_ml, torch::kFloat32);
-    CHECK_DT(*fa_query_start, torch::kInt32);
-    TORCH_CHECK(fa_query_start->numel() >= fa.S + 1, "fused attention: query_start needs S+1 entries");
-    fa.query_start = reinterpret_cast<const int32_t*>(fa_query_start->data_ptr());
-    fa.num_parts = (int)fa_part_o->size(2);
-    fa.part_size = (int)fa_part_size;
-    TORCH_CHECK((int64_t)fa.num_parts * fa_part_size >= fa_block_tables->size(1) * 16,
-                "fused attention: partitions do not cover max context");
-    TORCH_CHECK(fa_part_o->size(0) >= fa.S && fa_part_o->size(1) == hq, "fused attention: part_o shape");
-    fa.part_o = reinterpret_cast<float*>(fa_part_o->data_ptr());
-    fa.part_ml = reinterpret_cast<float*>(fa_part_ml->data_ptr());
-    CHECK_DEV(*fa_tickets); CHECK_DT(*fa_tickets, torch::kInt32);
-    TORCH_CHECK(fa_tickets->numel() >= (int64_t)fa.S * hkv, "fused attention: tickets need S*Hkv zeroed int32");
-    fa.tickets = reinterpret_cast<uint32_t*>(fa_tickets->data_ptr());
+    attn_set_parts(fa, *fa_part_o, *fa_part_ml, fa_part_size);
+    attn_set_queries(fa, fa_query_start);
+    attn_set_tickets(fa, fa_tickets);
+    TORCH_CHECK(fa.query_start && fa.tickets, "fused attention: query_start and tickets must be tensors");
+    attn_set_dbg(fa, fa_dbg_ts);  // (qa_phases.py)
     CHECK_DEV(*fa_sync); CHECK_DT(*fa_sync, torch::kInt32);
     TORCH_CHECK(fa_sync->is_contiguous(), "fused attention: granule buffer contiguous");
     fa.fault = g.fault;
-    if (fa_dbg_ts.has_value() && fa_dbg_ts->defined()) {  // profiling: attention phase stamps (qa_phases.py)
-      CHECK_DEV(*fa_dbg_ts); CHECK_DT(*fa_dbg_ts, torch::kInt64);
-      TORCH_CHECK(fa_dbg_ts->numel() >= 16, "fused attention: dbg_ts needs 16 int64");
-      fa.dbg_ts = reinterpret_cast<unsigned long long*>(fa_dbg_ts->data_ptr());
-    }
     g.fa = &fa;
     g.fa_gran = fa_sync->data_ptr();
     g.fa_gran_bytes = (size_t)fa_sync->numel() * 4;
@@ -321,54 +367,15 @@ void silu_mul(const Tensor& y, Tensor& out) {
                          cur_stream());
 }
 
-vgate::AttnArgs attn_common(const Tensor& q, int64_t q_stride, const Tensor& k_cache,
-                            const Tensor& v_cache, const Tensor& block_tables,
-                            const Tensor& context_lens, Tensor& out, int64_t Hq, int64_t Hkv,
-                            double scale) {
-  CHECK_DEV(q); CHECK_DEV(k_cache); CHECK_DEV(v_cache); CHECK_DEV(block_tables);
-  CHECK_DEV(context_lens); CHECK_DEV(out);
-  CHECK_DT(q, torch::kBFloat16); CHECK_DT(out, torch::kBFloat16);
-  CHECK_DT(block_tables, torch::kInt32); CHECK_DT(context_lens, torch::kInt32);
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16 && k_cache.size(3) == 128,
-              "attention: cache must be [nblk, Hkv, 16, 128]");
-  TORCH_CHECK(Hq % Hkv == 0 && Hq / Hkv <= 16, "attention: GQA group must be <= 16");
-  TORCH_CHECK(block_tables.is_contiguous(), "attention: block_tables contiguous");
-  vgate::AttnArgs a{};
-  a.q = bf16p(q); a.q_stride = (int)q_stride;
-  a.k_cache = bf16p(k_cache); a.v_cache = bf16p(v_cache);
-  a.block_tables = reinterpret_cast<const int32_t*>(block_tables.data_ptr());
-  a.max_blocks = (int)block_tables.size(1);
-  a.context_lens = reinterpret_cast<const int32_t*>(context_lens.data_ptr());
-  a.out = bf16p_mut(out); a.out_stride = (int)(Hq * 128);
-  TORCH_CHECK(out.is_contiguous(), "attention: out contiguous");
-  a.S = (int)context_lens.numel();
-  a.Hq = (int)Hq; a.Hkv = (int)Hkv; a.D = 128; a.BS = 16;
-  a.scale = (float)scale;
-  return a;
-}
-
 void attn_decode(const Tensor& q, int64_t q_stride, const Tensor& k_cache, const Tensor& v_cache,
                  const Tensor& block_tables, const Tensor& context_lens,
                  const c10::optional<Tensor>& query_start, Tensor& out, Tensor& part_o,
                  Tensor& part_ml, int64_t Hq, int64_t Hkv, int64_t part_size, double scale) {
   auto a = attn_common(q, q_stride, k_cache, v_cache, block_tables, context_lens, out, Hq, Hkv, scale);
-  CHECK_DT(part_o, torch::kFloat32); CHECK_DT(part_ml, torch::kFloat32);
-  TORCH_CHECK(part_size % 32 == 0 && part_size <= 1024, "attention: part_size must be a multiple of 32, <= 1024");
-  TORCH_CHECK(part_o.dim() == 4 && part_o.size(0) >= a.S && part_o.size(1) == Hq && part_o.size(3) == 128,
-              "attention: part_o must be [S, Hq, P, 128]");
-  a.num_parts = (int)part_o.size(2);
-  TORCH_CHECK((int64_t)a.num_parts * part_size >= block_tables.size(1) * 16,
-              "attention: partitions do not cover max context");
-  a.part_size = (int)part_size;
-  a.part_o = reinterpret_cast<float*>(part_o.data_ptr());
-  a.part_ml = reinterpret_cast<float*>(part_ml.data_ptr());
-  a.query_start = nullptr;
-  if (query_start.has_value() && query_start->defined()) {
-    CHECK_DT(*query_start, torch::kInt32);
-    a.query_start = reinterpret_cast<const int32_t*>(query_start->data_ptr());
-  }
+  attn_set_parts(a, part_o, part_ml, part_size);
+  attn_set_queries(a, query_start);
   c10::DeviceGuard guard(q.device());
-  vgate::launch_attn_decode(a, cur_stream());
+  vgate::launch_attention(a, a.S, cur_stream());  // num_tiles = 0: decode rows only
 }
 
 // the flash prefill K split's workspace: the GEMM workspace (ops.workspace), 65536 zeroed
@@ -391,13 +398,10 @@ void attn_prefill(const Tensor& q, int64_t q_stride, const Tensor& k_cache, cons
                   const c10::optional<Tensor>& fault) {
   auto a = attn_common(q, q_stride, k_cache, v_cache, block_tables, context_lens, out, Hq, Hkv, scale);
   set_flash_ws(a, flash_ws, fault);
-  CHECK_DT(query_start, torch::kInt32); CHECK_DT(tile_seq, torch::kInt32); CHECK_DT(tile_q0, torch::kInt32);
-  a.query_start = reinterpret_cast<const int32_t*>(query_start.data_ptr());
-  a.tile_seq = reinterpret_cast<const int32_t*>(tile_seq.data_ptr());
-  a.tile_q0 = reinterpret_cast<const int32_t*>(tile_q0.data_ptr());
-  a.num_tiles = (int)tile_seq.numel();
+  attn_set_queries(a, query_start);
+  attn_set_tiles(a, tile_seq, tile_q0);
   c10::DeviceGuard guard(q.device());
-  vgate::launch_attn_prefill(a, cur_stream());
+  vgate::launch_attention(a, 0, cur_stream());  // no decode rows
 }
 
 void attention(const Tensor& q, int64_t q_stride, const Tensor& k_cache, const Tensor& v_cache,
@@ -409,31 +413,11 @@ void attention(const Tensor& q, int64_t q_stride, const Tensor& k_cache, const T
   auto a = attn_common(q, q_stride, k_cache, v_cache, block_tables, context_lens, out, Hq, Hkv, scale);
   set_flash_ws(a, flash_ws, fault);
   if (out_stride > 0) a.out_stride = (int)out_stride;
-  CHECK_DT(query_start, torch::kInt32); CHECK_DT(tile_seq, torch::kInt32); CHECK_DT(tile_q0, torch::kInt32);
-  CHECK_DT(part_o, torch::kFloat32); CHECK_DT(part_ml, torch::kFloat32);
-  TORCH_CHECK(part_size % 32 == 0 && part_size <= 1024, "attention: part_size must be a multiple of 32, <= 1024");
-  TORCH_CHECK(query_start.numel() >= a.S + 1, "attention: query_start needs S+1 entries");
-  a.query_start = reinterpret_cast<const int32_t*>(query_start.data_ptr());
-  a.tile_seq = reinterpret_cast<const int32_t*>(tile_seq.data_ptr());
-  a.tile_q0 = reinterpret_cast<const int32_t*>(tile_q0.data_ptr());
-  a.num_tiles = (int)tile_seq.numel();
-  a.num_parts = (int)part_o.size(2);
-  a.part_size = (int)part_size;
-  TORCH_CHECK((int64_t)a.num_parts * part_size >= block_tables.size(1) * 16,
-              "attention: partitions do not cover max context");
-  TORCH_CHECK(part_o.size(0) >= a.S && part_o.size(1) == Hq, "attention: part_o shape");
-  a.part_o = reinterpret_cast<float*>(part_o.data_ptr());
-  a.part_ml = reinterpret_cast<float*>(part_ml.data_ptr());
-  if (tickets.has_value() && tickets->defined()) {
-    CHECK_DEV(*tickets); CHECK_DT(*tickets, torch::kInt32);
-    TORCH_CHECK(tickets->numel() >= (int64_t)a.S * Hkv, "attention: tickets need S*Hkv zeroed int32");
-    a.tickets = reinterpret_cast<uint32_t*>(tickets->data_ptr());
-  }
-  if (dbg_ts.has_value() && dbg_ts->defined()) {
-    CHECK_DEV(*dbg_ts); CHECK_DT(*dbg_ts, torch::kInt64);
-    TORCH_CHECK(dbg_ts->numel() >= 16, "attention: dbg_ts needs 16 int64");
-    a.dbg_ts = reinterpret_cast<unsigned long long*>(dbg_ts->data_ptr());
-  }
+  attn_set_parts(a, part_o, part_ml, part_size);
+  attn_set_queries(a, query_start);
+  attn_set_tiles(a, tile_seq, tile_q0);
+  attn_set_tickets(a, tickets);
+  attn_set_dbg(a, dbg_ts);
   c10::DeviceGuard guard(q.device());
   vgate::launch_attention(a, a.S, cur_stream());
 }

@@ -65,7 +65,8 @@ class Dev:
 
 
 def _has_flash(Hq, Hkv) -> bool:
-    """attention.hip flash_cfg: 8 waves when G divides 8, 6 when it divides 6, else the tile kernel."""
+    """attention.hip flash_cfg: 8 waves when G divides 8, 6 when it divides 6, else the tile kernel.
+    (The same head-group rule as flash_cfg and ops.flash_lead: change the three together.)"""
     G = Hq // Hkv
     return 8 % G == 0 or 6 % G == 0
 

@@ -565,6 +565,74 @@ def test_qkv_attention_fused(hq, hkv, S, mode):
     assert fused & set(names), names  # the decode kernel took the fused launch
 
 
+def test_attention_bindings_reject_bad_buffers():
+    """The attention entry points (attn_decode, attn_prefill, attention, gemm's fused attention) share
+    one set of buffer checks: each malformed split-K / query_start buffer raises before any launch, and
+    the well-formed call of the same tiny case still matches the fp32 reference."""
+    torch.manual_seed(77)
+    Hq, Hkv, S, D, BS, part, H = 4, 2, 2, 128, 16, 32, 1536
+    C = ops.native()
+    kc, vc = _make_cache(8, Hkv, seed=3)
+    bt = torch.tensor([[1, 2], [3, 4]], dtype=torch.int32, device=DEV)  # 2 blocks: one 32-token partition
+    bt_wide = torch.tensor([[1, 2, 5], [3, 4, 6]], dtype=torch.int32, device=DEV)  # 48 tokens > P * part
+    cl = torch.tensor([20, 20], dtype=torch.int32, device=DEV)
+    qs = torch.arange(S + 1, dtype=torch.int32, device=DEV)
+    q = torch.randn(S, Hq * D, device=DEV).bfloat16()
+    e = torch.empty(0, dtype=torch.int32, device=DEV)
+    ts = torch.tensor([0, 1], dtype=torch.int32, device=DEV)  # one tile per (single-query) sequence
+    tq = torch.zeros(2, dtype=torch.int32, device=DEV)
+    scale = D ** -0.5
+    good = dict(po=torch.empty(S, Hq, 1, D, device=DEV), pml=torch.empty(S, Hq, 1, 2, device=DEV), part=part, bt=bt,
+                qs=qs)
+    bad = {"part_o of 3 dimensions": dict(po=torch.empty(S, Hq, D, device=DEV)),
+           "part_o with last dimension 64": dict(po=torch.empty(S, Hq, 1, 64, device=DEV)),
+           "part_ml of half the elements": dict(pml=torch.empty(S, Hq, 1, 1, device=DEV)),
+           "part_size 48": dict(part=48),
+           "partitions short of the page table": dict(bt=bt_wide)}
+    short_qs = {"query_start one entry short": dict(qs=qs[:S].contiguous())}
+    # the fused path: the decode QKV projection of x, its q and the new K / V rows (position 19)
+    x = torch.randn(S, H, device=DEV).bfloat16()
+    gamma = (torch.rand(H, device=DEV) + 0.5).bfloat16()
+    lin = ops.Linear((torch.randn((Hq + 2 * Hkv) * D, H, device=DEV) / math.sqrt(H)).bfloat16(), layout="qkv")
+    assert lin.fold_norm(gamma)
+    cs = ref.rope_cos_sin(64, D, 1e6, device=DEV)
+    pos = cl - 1
+    slots = (bt[torch.arange(S, device=DEV), (pos // BS).long()] * BS + pos % BS).int()
+
+    def decode(out, a):
+        C.attn_decode(q, Hq * D, kc, vc, a["bt"], cl, a["qs"], out, a["po"], a["pml"], Hq, Hkv, a["part"], scale)
+
+    def unified(out, a):
+        C.attention(q, Hq * D, kc, vc, a["bt"], cl, a["qs"], e, e, out, a["po"], a["pml"], Hq, Hkv, a["part"], scale)
+
+    def prefill(out, a):
+        C.attn_prefill(q, Hq * D, kc, vc, a["bt"], cl, a["qs"], ts, tq, out, Hq, Hkv, scale)
+
+    fused_q, fused_kv = torch.empty(S, Hq * D, dtype=torch.bfloat16, device=DEV), (kc.clone(), vc.clone())
+
+    def fused(out, a):
+        ops.linear(x, lin, out=fused_q, norm=(gamma, 1e-6),
+                   qkv=dict(positions=pos, slots=slots, cos_sin=cs, k_cache=fused_kv[0], v_cache=fused_kv[1], hq=Hq,
+                            hkv=Hkv),
+                   attn=dict(block_tables=a["bt"], context_lens=cl, query_start=a["qs"], out=out, part_o=a["po"],
+                             part_ml=a["pml"], part_size=a["part"], scale=scale))
+
+    for fn, cases in ((decode, bad), (unified, {**bad, **short_qs}), (fused, bad), (prefill, short_qs)):
+        for what, change in cases.items():
+            with pytest.raises(RuntimeError):
+                fn(torch.zeros(S, Hq * D, device=DEV).bfloat16(), {**good, **change})
+                pytest.fail(f"{fn.__name__} accepted {what}")
+    r = ref.attention_ref(q.view(S, Hq, D), kc, vc, bt, cl, qs.cpu(), Hq, Hkv, scale)
+    for fn in (decode, unified, prefill):
+        out = torch.zeros(S, Hq * D, device=DEV).bfloat16()
+        fn(out, good)
+        assert _rel_err(out.view(S, Hq, D), r) < 2e-2, fn.__name__
+    out = torch.zeros(S, Hq * D, device=DEV).bfloat16()
+    fused(out, good)
+    rf = ref.attention_ref(fused_q.view(S, Hq, D), *fused_kv, bt, cl, qs.cpu(), Hq, Hkv, scale)
+    assert _rel_err(out, rf.view(S, Hq * D)) < 1e-2
+
+
 def test_awq_norm_splitk():
     torch.manual_seed(13)
     M, N, K, g = 8, 1536, 1536, 128

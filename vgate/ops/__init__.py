@@ -302,7 +302,8 @@ def prefill_tiles(query_lens: list[int], lead: int = 32) -> tuple[list[int], lis
 def flash_lead(hq: int, hkv: int) -> int:
     """Queries per flash-prefill block for a head layout (attention.hip flash_cfg: 8 waves when
     G = hq / hkv divides 8, else 6; two 16-query column tiles per wave up to G = 4, one above;
-    the waves are G heads x NW / G query groups)."""
+    the waves are G heads x NW / G query groups). Restated here so that it works without the native
+    module; tests/test_attn_probe_gpu.py _has_flash is the third copy: change the three together."""
     G = max(1, hq // max(hkv, 1))
     nw = 8 if 8 % G == 0 else (6 if 6 % G == 0 else 0)
     if nw == 0:
