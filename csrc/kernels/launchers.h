@@ -201,6 +201,13 @@ void launch_rope_kv(uint16_t* qkv, const int32_t* positions, const int32_t* slot
                     const float* cos_sin, uint16_t* k_cache, uint16_t* v_cache, int T, int Hq,
                     int Hkv, int D, int BS, hipStream_t st,
                     uint16_t* q_out = nullptr, int ldq = 0);
+// Per-head QK-norm (RMSNorm over each q / k head's 128 dims, weights q_norm / k_norm [128]) + NeoX RoPE
+// + paged KV-cache write (qk_norm.hip). qkv [T, (Hq + 2*Hkv) * 128] is read only; normed, rotated q ->
+// q_out (row stride ldq), k -> k_cache, v unchanged -> v_cache; slot < 0 => q only. D = 128.
+void launch_qk_norm_rope_kv(const uint16_t* qkv, const int32_t* positions, const int32_t* slots,
+                            const float* cos_sin, const uint16_t* q_norm, const uint16_t* k_norm, float eps,
+                            uint16_t* k_cache, uint16_t* v_cache, int T, int Hq, int Hkv, int BS,
+                            uint16_t* q_out, int ldq, hipStream_t st);
 void launch_silu_mul(const uint16_t* y, int ldy, uint16_t* out, int ldo, int I, int M, hipStream_t st);
 
 struct AttnArgs {

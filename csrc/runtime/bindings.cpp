@@ -354,6 +354,56 @@ void rope_kv(Tensor& qkv, const Tensor& positions, const c10::optional<Tensor>& 
                         cur_stream(), qo, ldq);
 }
 
+// Qwen3 QK-norm: per-head RMSNorm of q / k, NeoX RoPE, paged KV write (qk_norm.hip). qkv is read only.
+void qk_norm_rope_kv(const Tensor& qkv, const Tensor& positions, const c10::optional<Tensor>& slots,
+                     const Tensor& cos_sin, const Tensor& q_norm, const Tensor& k_norm, double eps,
+                     Tensor& k_cache, Tensor& v_cache, int64_t Hq, int64_t Hkv, Tensor& q_out) {
+  constexpr int64_t D = 128;
+  CHECK_DEV(qkv); CHECK_DEV(positions); CHECK_DEV(cos_sin); CHECK_DEV(q_norm); CHECK_DEV(k_norm);
+  CHECK_DEV(k_cache); CHECK_DEV(v_cache); CHECK_DEV(q_out);
+  CHECK_DT(qkv, torch::kBFloat16); CHECK_DT(positions, torch::kInt32); CHECK_DT(cos_sin, torch::kFloat32);
+  CHECK_DT(q_norm, torch::kBFloat16); CHECK_DT(k_norm, torch::kBFloat16);
+  CHECK_DT(k_cache, torch::kBFloat16); CHECK_DT(v_cache, torch::kBFloat16); CHECK_DT(q_out, torch::kBFloat16);
+  TORCH_CHECK(Hq >= 1 && Hkv >= 1, "qk_norm_rope_kv: Hq, Hkv >= 1");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.is_contiguous() && qkv.size(1) == (Hq + 2 * Hkv) * D,
+              "qk_norm_rope_kv: qkv must be contiguous [T, (Hq + 2 Hkv) * 128] (head_dim 128 only)");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(positions.is_contiguous() && positions.numel() >= T, "qk_norm_rope_kv: positions needs >= T entries");
+  const int32_t* sp = nullptr;
+  if (slots.has_value() && slots->defined()) {
+    CHECK_DEV(*slots); CHECK_DT(*slots, torch::kInt32);
+    TORCH_CHECK(slots->is_contiguous() && slots->numel() >= T, "qk_norm_rope_kv: slots needs >= T entries");
+    TORCH_CHECK(slots->device() == qkv.device(), "qk_norm_rope_kv: slots on another device");
+    sp = reinterpret_cast<const int32_t*>(slots->data_ptr());
+  }
+  TORCH_CHECK(q_norm.numel() == D && k_norm.numel() == D && q_norm.is_contiguous() && k_norm.is_contiguous(),
+              "qk_norm_rope_kv: q_norm / k_norm must be bf16 [128]");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.is_contiguous() && cos_sin.size(1) == D,
+              "qk_norm_rope_kv: cos_sin must be [max_pos, 128]");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(1) == Hkv && k_cache.size(3) == D && k_cache.is_contiguous() &&
+                  v_cache.sizes() == k_cache.sizes() && v_cache.is_contiguous(),
+              "qk_norm_rope_kv: caches must be contiguous [blocks, Hkv, BS, 128]");
+  CHECK_LASTDIM(q_out);
+  TORCH_CHECK(q_out.dim() == 2 && q_out.size(0) >= T && q_out.size(1) >= Hq * D, "qk_norm_rope_kv: q_out shape");
+  // 8-B quads of q_out, 16-B vectors of qkv / the caches, 16-B cos / sin quads
+  TORCH_CHECK(q_out.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(q_out.data_ptr()) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(cos_sin.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q_norm.data_ptr()) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(k_norm.data_ptr()) % 8 == 0,
+              "qk_norm_rope_kv: operand alignment");
+  for (const Tensor* t : {&positions, &cos_sin, &q_norm, &k_norm, (const Tensor*)&k_cache, (const Tensor*)&v_cache,
+                          (const Tensor*)&q_out})
+    TORCH_CHECK(t->device() == qkv.device(), "qk_norm_rope_kv: every tensor must be on qkv's device");
+  c10::DeviceGuard guard(qkv.device());
+  vgate::launch_qk_norm_rope_kv(bf16p(qkv), reinterpret_cast<const int32_t*>(positions.data_ptr()), sp,
+                                reinterpret_cast<const float*>(cos_sin.data_ptr()), bf16p(q_norm), bf16p(k_norm),
+                                (float)eps, bf16p_mut(k_cache), bf16p_mut(v_cache), (int)T, (int)Hq, (int)Hkv,
+                                (int)k_cache.size(2), bf16p_mut(q_out), (int)q_out.stride(0), cur_stream());
+}
+
 // out [M, I] = silu(y[:, :I]) * y[:, I:2I]
 void silu_mul(const Tensor& y, Tensor& out) {
   CHECK_DEV(y); CHECK_DEV(out);
@@ -690,6 +740,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("rope_kv", &rope_kv, "NeoX RoPE + paged KV-cache write (rotated q in place or into q_out)",
         py::arg("qkv"), py::arg("positions"), py::arg("slots"), py::arg("cos_sin"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"), py::arg("q_out") = py::none());
+  m.def("qk_norm_rope_kv", &qk_norm_rope_kv,
+        "per-head QK-norm (RMSNorm over 128 dims) + NeoX RoPE + paged KV-cache write; qkv is read only",
+        py::arg("qkv"), py::arg("positions"), py::arg("slots"), py::arg("cos_sin"), py::arg("q_norm"),
+        py::arg("k_norm"), py::arg("eps"), py::arg("k_cache"), py::arg("v_cache"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("q_out"));
   m.def("awq_dequant", &awq_dequant, "AWQ int4 packed -> bf16 fragment-packed (prefill operand; optional gamma fold)",
         py::arg("wq"), py::arg("scales"), py::arg("sz"), py::arg("N"), py::arg("K"), py::arg("group"), py::arg("out"),
         py::arg("gamma") = py::none());

@@ -17,6 +17,13 @@ Per layer (TP degree t, Megatron layout):
 The residual add of a row-parallel GEMM is applied by TP rank 0 only, so the
 all-reduce of the partial outputs yields resid + sum(partials) on every rank
 with no extra kernel.
+
+QK-norm families (``arch.qk_norm``: Qwen3) put an RMSNorm over each head's 128 dims between the
+projection and RoPE. A head's columns are spread over eight tiles of the fused QKV epilogue, so the
+norm cannot ride there: the projection is a plain-layout GEMM into a [T, (hq + 2 hkv) * 128] buffer
+and one more launch (ops.qk_norm_rope_kv, csrc/kernels/qk_norm.hip) norms, rotates and writes q and
+the KV cache. Such a layer is 6 launches (qkv, qk_norm_rope_kv, attention, o, gate_up, down) on every
+step; the fused qkv + decode-attention launch is not used. Other families launch what they always did.
 """
 from __future__ import annotations
 
@@ -46,6 +53,9 @@ class LayerWeights:
     post_norm: torch.Tensor
     gate_up: ops.Linear
     down: ops.Linear
+    # QK-norm weights [head_dim] (arch.qk_norm: Qwen3), replicated on every TP rank
+    q_norm: torch.Tensor | None = None
+    k_norm: torch.Tensor | None = None
 
 
 class ShardSpec:
@@ -100,6 +110,11 @@ class DecoderModel:
         else:
             from vgate.models.weights import random_init
             random_init(self, seed)
+        if arch.qk_norm:
+            for L in self.layers:
+                if L.q_norm is None or L.k_norm is None or L.qkv.layout != "plain":
+                    raise ValueError("qk_norm: every layer needs q_norm / k_norm and a plain-layout QKV projection")
+                L.qkv.norm_in = True
         if self.device.type == "cuda" and self.quant == "awq":
             # long AWQ steps: int4 -> bf16 dequant of one matrix at a time into a shared scratch
             # (ops.linear), sized once here so graph capture never allocates
@@ -142,6 +157,8 @@ class DecoderModel:
         n = self.embed.numel() * 2 + self.final_norm.numel() * 2 + self.lm_head.nbytes()
         for L in self.layers:
             n += L.qkv.nbytes() + L.o.nbytes() + L.gate_up.nbytes() + L.down.nbytes() + 4 * L.in_norm.numel()
+            if L.q_norm is not None:
+                n += 2 * (L.q_norm.numel() + L.k_norm.numel())
         return n
 
     # ---------------------------------------------------------------- forward
@@ -193,7 +210,8 @@ class DecoderModel:
         Returns f32 logits [S, vocab] for the sample rows (one per sequence), or with
         ``return_hidden`` the residual stream [T, H] after the last layer (embeddings).
         GPU: 4 fused GEMM launches + 1 attention launch per layer (RMSNorm, RoPE, KV
-        write, bias, SiLU*mul and residual adds all live inside them).
+        write, bias, SiLU*mul and residual adds all live inside them). QK-norm families: a plain QKV
+        GEMM plus the qk_norm_rope_kv launch in place of the fused QKV epilogue (module docstring).
         """
         if self.device.type != "cuda":
             return self._forward_reference(sv, kv_caches, part_size, return_hidden)
@@ -210,6 +228,9 @@ class DecoderModel:
             tp.all_reduce(resid)
         q = torch.empty(T, sh.hq * D, dtype=torch.bfloat16, device=dev)
         attn = torch.empty(T, sh.hq * D, dtype=torch.bfloat16, device=dev)
+        # QK-norm: the plain projection's [q | k | v] rows, read by ops.qk_norm_rope_kv (allocated here,
+        # not per layer, so graph capture sees one buffer)
+        qkv_buf = torch.empty(T, (sh.hq + 2 * sh.hkv) * D, dtype=torch.bfloat16, device=dev) if a.qk_norm else None
         mlp = torch.empty(T, sh.inter, dtype=torch.bfloat16, device=dev)
         P = max(1, (self.max_model_len + part_size - 1) // part_size)
         part_o = torch.empty(S, sh.hq, P, D, dtype=torch.float32, device=dev)
@@ -236,18 +257,23 @@ class DecoderModel:
 
         # decode-only steps (T <= S: no prefill tiles, StepMeta.tile_cap): the decode attention rides in
         # the QKV projection's launch (ops.linear attn=, csrc/kernels/qkv_attn.hip)
-        fuse_attn = T <= S and T <= 16
+        # (QK-norm layers: the norm sits between the projection and the attention, in its own launch)
+        fuse_attn = T <= S and T <= 16 and not a.qk_norm
         for li, L in enumerate(self.layers):
             kc, vc = kv_caches[li]
             qkv_args = dict(positions=sv.positions, slots=sv.slots, cos_sin=self.cos_sin, k_cache=kc, v_cache=vc,
-                            hq=sh.hq, hkv=sh.hkv)
+                            hq=sh.hq, hkv=sh.hkv) if not a.qk_norm else None
             fa = dict(block_tables=sv.block_tables, context_lens=sv.context_lens, query_start=sv.query_start,
                       out=attn, part_o=part_o, part_ml=part_ml, part_size=part_size,
                       scale=self.scale) if fuse_attn else None
+            proj_out = qkv_buf if a.qk_norm else q
             if li > 0 and takes(L.qkv):
-                ops.linear(hg if awq else resid, L.qkv, out=q, prenorm=(ssp, eps), qkv=qkv_args, attn=fa)
+                ops.linear(hg if awq else resid, L.qkv, out=proj_out, prenorm=(ssp, eps), qkv=qkv_args, attn=fa)
             else:
-                ops.linear(resid, L.qkv, out=q, norm=(L.in_norm, eps), qkv=qkv_args, attn=fa)
+                ops.linear(resid, L.qkv, out=proj_out, norm=(L.in_norm, eps), qkv=qkv_args, attn=fa)
+            if a.qk_norm:
+                ops.qk_norm_rope_kv(qkv_buf, sv.positions, sv.slots, self.cos_sin, L.q_norm, L.k_norm, eps, kc, vc,
+                                    sh.hq, sh.hkv, q)
             if fa is None:
                 ops.attention(q, sh.hq * D, kc, vc, sv.block_tables, sv.context_lens, sv.query_start, sv.tile_seq,
                               sv.tile_q0, attn, part_o, part_ml, sh.hq, sh.hkv, part_size, self.scale)
@@ -282,14 +308,20 @@ class DecoderModel:
         x = torch.empty_like(resid)
         attn = torch.empty(T, sh.hq * D, dtype=act, device=dev)
         qkv = torch.empty(T, (sh.hq + 2 * sh.hkv) * D, dtype=act, device=dev)
+        q = torch.empty(T, sh.hq * D, dtype=act, device=dev) if a.qk_norm else None
         mlp = torch.empty(T, sh.inter, dtype=act, device=dev)
         first = tp.is_first
         for li, L in enumerate(self.layers):
             kc, vc = kv_caches[li]
             ops.rmsnorm(resid, L.in_norm, a.rms_eps, out=x)
             ops.linear(x, L.qkv, out=qkv)
-            ops.rope_kv(qkv, sv.positions, sv.slots, self.cos_sin, kc, vc, sh.hq, sh.hkv, D)
-            self._attention_cpu(qkv, attn, kc, vc, sv)
+            if a.qk_norm:
+                ops.qk_norm_rope_kv(qkv, sv.positions, sv.slots, self.cos_sin, L.q_norm, L.k_norm, a.rms_eps, kc, vc,
+                                    sh.hq, sh.hkv, q)
+                self._attention_cpu(q, attn, kc, vc, sv)
+            else:
+                ops.rope_kv(qkv, sv.positions, sv.slots, self.cos_sin, kc, vc, sh.hq, sh.hkv, D)
+                self._attention_cpu(qkv, attn, kc, vc, sv)
             self._row_parallel(attn, L.o, resid, first)
             ops.rmsnorm(resid, L.post_norm, a.rms_eps, out=x)
             ops.linear(x, L.gate_up, out=mlp)
@@ -353,6 +385,8 @@ class DecoderModel:
             q = qkv[:, : a.q_size].view(n, a.num_heads, D)
             k = qkv[:, a.q_size: a.q_size + a.kv_size].view(n, a.num_kv_heads, D)
             v = qkv[:, a.q_size + a.kv_size:].view(n, a.num_kv_heads, D)
+            if a.qk_norm:  # HF order: RMSNorm per head, then RoPE
+                q, k = norm(q, L.q_norm), norm(k, L.k_norm)
             q, k = rope(q), rope(k)
             k = k.repeat_interleave(G, 1)
             v = v.repeat_interleave(G, 1)

@@ -40,6 +40,14 @@ def _rand_awq(N, K, group, g, device, silu=False, layout="plain"):
                                  "layout": "silu" if silu else layout})
 
 
+QK_NORM_LO, QK_NORM_HI = 0.5, 4.0  # random-init range of the QK-norm weights (random_init)
+
+
+def _rand_qk_norm(D, g, device):
+    u = torch.rand(D, generator=g, device=device, dtype=torch.float32)
+    return (QK_NORM_LO + (QK_NORM_HI - QK_NORM_LO) * u).to(torch.bfloat16)
+
+
 def random_init(model, seed: int = 0) -> None:
     a: ModelArch = model.arch
     sh = model.shard
@@ -52,22 +60,31 @@ def random_init(model, seed: int = 0) -> None:
     layers = []
     from vgate.models.transformer import LayerWeights
     q_out = (sh.hq + 2 * sh.hkv) * D
+    # QK-norm archs: the projection keeps its natural rows (the norm's own kernel rotates), and the two
+    # norm weights come from a generator of their own, after the layer's other draws: they are replicated,
+    # so the stream must not depend on the TP rank, and every other preset's stream stays as it was.
+    # Uniform in [QK_NORM_LO, QK_NORM_HI] per element: a wide, non-constant range makes attention sharp,
+    # as trained Qwen3 norms do, and a dropped or misplaced norm visible in the tokens.
+    qkv_layout = "plain" if a.qk_norm else "qkv"
+    gn = _gen(dev, seed * 1000003 + 500009) if a.qk_norm else None
     for _ in range(a.num_layers):
         qkv_b = _randn((q_out,), 0.02, g, dev) if a.qkv_bias else None
         if awq and H % 128 == 0 and (sh.hq * D) % 128 == 0 and sh.inter % 128 == 0:
-            qkv = _rand_awq(q_out, H, group, g, dev, layout="qkv")
+            qkv = _rand_awq(q_out, H, group, g, dev, layout=qkv_layout)
             qkv.bias = qkv_b
             o = _rand_awq(H, sh.hq * D, group, g, dev)
             gu = _rand_awq(2 * sh.inter, H, group, g, dev, silu=True)
             down = _rand_awq(H, sh.inter, group, g, dev)
         else:
-            qkv = ops.Linear(_randn((q_out, H), 1 / math.sqrt(H), g, dev), bias=qkv_b, layout="qkv")
+            qkv = ops.Linear(_randn((q_out, H), 1 / math.sqrt(H), g, dev), bias=qkv_b, layout=qkv_layout)
             o = ops.Linear(_randn((H, sh.hq * D), 1 / math.sqrt(sh.hq * D * sh.tp.size), g, dev))
             gu = ops.Linear(_randn((2 * sh.inter, H), 1 / math.sqrt(H), g, dev), kind="silu")
             down = ops.Linear(_randn((H, sh.inter), 1 / math.sqrt(sh.inter * sh.tp.size), g, dev))
+        qn, kn = (_rand_qk_norm(D, gn, dev), _rand_qk_norm(D, gn, dev)) if a.qk_norm else (None, None)
         layers.append(LayerWeights(
             in_norm=torch.ones(H, dtype=torch.bfloat16, device=dev), qkv=qkv, o=o,
-            post_norm=torch.ones(H, dtype=torch.bfloat16, device=dev), gate_up=gu, down=down))
+            post_norm=torch.ones(H, dtype=torch.bfloat16, device=dev), gate_up=gu, down=down,
+            q_norm=qn, k_norm=kn))
         if awq and dev.type == "cuda":
             torch.cuda.empty_cache()
     model.layers = layers
@@ -129,7 +146,7 @@ def _rows(t: torch.Tensor, a: int, b: int) -> torch.Tensor:
 
 
 def load_checkpoint(model, path: str) -> None:
-    """Load an HF Qwen2/Llama checkpoint (safetensors) for this TP rank."""
+    """Load an HF Qwen2 / Qwen3 / Llama checkpoint (safetensors) for this TP rank."""
     a: ModelArch = model.arch
     sh = model.shard
     dev = model.device
@@ -166,6 +183,7 @@ def load_checkpoint(model, path: str) -> None:
         return ops.Linear(None, awq={"qint": q, "scales": s.to(dev), "zeros": z.to(dev), "group": group,
                                      "layout": "silu" if silu else layout})
 
+    qkv_layout = "plain" if a.qk_norm else "qkv"  # QK-norm: natural rows, see random_init
     qa, qb = sh.q_head0 * D, (sh.q_head0 + sh.hq) * D
     ka, kb = a.q_size + sh.kv_head0 * D, a.q_size + (sh.kv_head0 + sh.hkv) * D
     va, vb = a.q_size + a.kv_size + sh.kv_head0 * D, a.q_size + a.kv_size + (sh.kv_head0 + sh.hkv) * D
@@ -183,7 +201,7 @@ def load_checkpoint(model, path: str) -> None:
             k = awq_rows(att + ".k_proj", [(ka - a.q_size, kb - a.q_size)])
             v = awq_rows(att + ".v_proj", [(va - a.q_size - a.kv_size, vb - a.q_size - a.kv_size)])
             qkv = make_awq((torch.cat([q[0], k[0], v[0]]), torch.cat([q[1], k[1], v[1]], 1),
-                            torch.cat([q[2], k[2], v[2]], 1)), layout="qkv")
+                            torch.cat([q[2], k[2], v[2]], 1)), layout=qkv_layout)
             qkv.bias = bias
             o = make_awq(awq_cols(att + ".o_proj", qa, qb))
             g_ = awq_rows(mlp + ".gate_proj", [(sh.inter0, sh.inter0 + sh.inter)])
@@ -195,14 +213,23 @@ def load_checkpoint(model, path: str) -> None:
             wq = dense(att + ".q_proj.weight")[qa:qb]
             wk = dense(att + ".k_proj.weight")[ka - a.q_size: kb - a.q_size]
             wv = dense(att + ".v_proj.weight")[va - a.q_size - a.kv_size: vb - a.q_size - a.kv_size]
-            qkv = ops.Linear(torch.cat([wq, wk, wv]).to(dev), bias=bias, layout="qkv")
+            qkv = ops.Linear(torch.cat([wq, wk, wv]).to(dev), bias=bias, layout=qkv_layout)
             o = ops.Linear(dense(att + ".o_proj.weight")[:, qa:qb].contiguous().to(dev))
             wg = dense(mlp + ".gate_proj.weight")[sh.inter0: sh.inter0 + sh.inter]
             wu = dense(mlp + ".up_proj.weight")[sh.inter0: sh.inter0 + sh.inter]
             gu = ops.Linear(torch.cat([wg, wu]).to(dev), kind="silu")
             down = ops.Linear(dense(mlp + ".down_proj.weight")[:, sh.inter0: sh.inter0 + sh.inter].contiguous().to(dev))
+        qn = kn = None
+        if a.qk_norm:  # [head_dim] each, shared by every head: replicated on every TP rank
+            missing = [k for k in (att + ".q_norm.weight", att + ".k_norm.weight") if not idx.has(k)]
+            if missing:
+                raise ValueError(f"{root}: the architecture has QK-norm (model_type qwen3) but the checkpoint "
+                                 f"lacks {missing}")
+            qn, kn = dense(att + ".q_norm.weight").to(dev), dense(att + ".k_norm.weight").to(dev)
+            if qn.numel() != D or kn.numel() != D:
+                raise ValueError(f"{att}: q_norm / k_norm must have head_dim = {D} elements")
         layers.append(LayerWeights(dense(p + ".input_layernorm.weight").to(dev), qkv, o,
-                                   dense(p + ".post_attention_layernorm.weight").to(dev), gu, down))
+                                   dense(p + ".post_attention_layernorm.weight").to(dev), gu, down, qn, kn))
     model.layers = layers
     emb = dense("model.embed_tokens.weight")
     pad = sh.vocab_padded - emb.shape[0]
@@ -244,6 +271,9 @@ def save_checkpoint(model, path: str) -> None:
         out[p + ".mlp.down_proj.weight"] = L.down.dense_weight().cpu().contiguous()
         out[p + ".input_layernorm.weight"] = L.in_norm.cpu()
         out[p + ".post_attention_layernorm.weight"] = L.post_norm.cpu()
+        if L.q_norm is not None:
+            out[p + ".self_attn.q_norm.weight"] = L.q_norm.cpu()
+            out[p + ".self_attn.k_norm.weight"] = L.k_norm.cpu()
     if not a.tie_embeddings:
         out["lm_head.weight"] = model.lm_head.dense_weight()[: a.vocab_size].cpu().contiguous()
     Path(path).mkdir(parents=True, exist_ok=True)

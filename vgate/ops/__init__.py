@@ -266,6 +266,19 @@ def rope_kv(qkv, positions, slots, cos_sin, k_cache, v_cache, Hq: int, Hkv: int,
     native().rope_kv(qkv, positions, slots, cos_sin, k_cache, v_cache, Hq, Hkv, D)
 
 
+def qk_norm_rope_kv(qkv, positions, slots, cos_sin, q_norm, k_norm, eps: float, k_cache, v_cache, Hq: int, Hkv: int,
+                    q_out) -> None:
+    """Qwen3 QK-norm behind a plain QKV projection (csrc/kernels/qk_norm.hip): per-head RMSNorm of the
+    q / k heads of ``qkv`` [T, (Hq + 2 Hkv) * 128] with ``q_norm`` / ``k_norm`` [128], NeoX RoPE, q ->
+    ``q_out`` [>= T, >= Hq * 128], k and v -> the paged cache (slots < 0: q only). ``qkv`` is read only."""
+    if not _gpu(qkv):
+        ref.qk_norm_rope_kv_ref(qkv, positions, slots, cos_sin, q_norm, k_norm, eps, k_cache, v_cache, Hq, Hkv, 128,
+                                q_out)
+        return
+    native().qk_norm_rope_kv(qkv, positions, slots, cos_sin, q_norm, k_norm, float(eps), k_cache, v_cache, Hq, Hkv,
+                             q_out)
+
+
 def attention_decode(q, q_stride, k_cache, v_cache, block_tables, context_lens, out, part_o, part_ml,
                      Hq: int, Hkv: int, part_size: int, scale: float, query_start=None):
     """One query token per sequence. q rows index = sequence (or query_start[s+1]-1)."""
@@ -422,7 +435,7 @@ def softmax_scale(head_dim: int) -> float:
 __all__ = [
     "native", "native_available", "pack_weight", "unpack_weight", "interleave_gate_up", "pack_awq",
     "Linear", "linear", "attention", "workspace", "fault_word", "reset_handoffs",
-    "row_permutation", "reserve_awq_scratch", "pack_awq_sz", "rmsnorm", "embedding", "rope_kv", "attention_decode", "attention_prefill",
+    "row_permutation", "reserve_awq_scratch", "pack_awq_sz", "rmsnorm", "embedding", "rope_kv", "qk_norm_rope_kv", "attention_decode", "attention_prefill",
     "prefill_tiles", "sample", "logprobs", "logprob_views", "softmax_scale", "ref", "host_device_copy", "tune_prefill", "apply_prefill_plans",
 ]
 

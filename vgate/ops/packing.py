@@ -107,6 +107,9 @@ class Linear:
         self.kind = "awq" if awq is not None else "dense"
         self.bias = bias
         self.norm_gamma = None  # RMSNorm weight folded into the packed copy (see fold_norm)
+        # a plain-layout Linear whose input is RMSNormed in its launch (a QK-norm model's QKV projection;
+        # "qkv" / "silu" layouts always are): the tuner times its candidates with the row scale
+        self.norm_in = False
         # decode-GEMM decomposition for M <= 16 steps (0 = the launcher's heuristic): set by the
         # model from the measured per-shape table (vgate/models/decode_plans.py)
         self.dec_waves = 0

@@ -100,6 +100,35 @@ def rope_kv_ref(qkv, positions, slots, cos_sin, k_cache, v_cache, Hq, Hkv, D):
         v_cache[blk, :, off] = v3[idx, Hq + Hkv:]
 
 
+def qk_norm_rope_kv_ref(qkv, positions, slots, cos_sin, q_norm, k_norm, eps, k_cache, v_cache, Hq, Hkv, D, q_out):
+    """Qwen3 QK-norm: RMSNorm over each q / k head's D dims (weights q_norm / k_norm [D]), then NeoX
+    rotary; q -> q_out[:, :Hq*D], k and the unchanged v -> the paged cache (slots < 0: q only). fp32
+    from the inputs to one rounding to qkv.dtype (fp32 activations: nothing rounds); qkv is not modified."""
+    T = qkv.shape[0]
+    if T == 0:
+        return
+    v3 = qkv.view(T, Hq + 2 * Hkv, D)
+    half = D // 2
+    x = v3[:, : Hq + Hkv].float()
+    gamma = torch.cat([q_norm.float().reshape(1, D).expand(Hq, D), k_norm.float().reshape(1, D).expand(Hkv, D)])
+    n = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps) * gamma
+    cs = cos_sin[positions[:T].long()]  # [T, D]
+    c, s = cs[:, None, :half], cs[:, None, half:]
+    n1, n2 = n[..., :half], n[..., half:]
+    rot = torch.cat([n1 * c - n2 * s, n2 * c + n1 * s], dim=-1).to(qkv.dtype)
+    q_out[:T, : Hq * D] = rot[:, :Hq].reshape(T, Hq * D)
+    if slots is None:
+        return
+    BS = k_cache.shape[2]
+    sl = slots[:T].long()
+    ok = sl >= 0
+    if ok.any():
+        idx = torch.nonzero(ok).squeeze(-1)
+        blk, off = sl[idx] // BS, sl[idx] % BS
+        k_cache[blk, :, off] = rot[idx, Hq:].to(k_cache.dtype)
+        v_cache[blk, :, off] = v3[idx, Hq + Hkv:].to(v_cache.dtype)
+
+
 def _gather_kv(cache, table_row, n):
     BS = cache.shape[2]
     nb = (n + BS - 1) // BS

@@ -138,7 +138,9 @@ def tune_prefill(lins: list, ms: list[int], iters: int = 5, margin: float = TUNE
         # the folded RMSNorm's row scale as in the step (qkv / gate_up: the x^2 sums ride in the K loop
         # and cost some kernels up to ~30 % more than others — 128 x 320 tiles with four wave columns:
         # Qwen2.5-1.5B qkv at 448 rows 17.7 -> 22.9 us, profiles/r6_tuner_norm_timing.log)
-        nkw = dict(rownorm=True, eps=1e-6) if lin.norm_gamma is not None or lin.layout in ("qkv", "silu") else {}
+        # (a QK-norm model's QKV projection is a plain-layout Linear that still takes the row scale: Linear.norm_in)
+        nkw = (dict(rownorm=True, eps=1e-6)
+               if lin.norm_gamma is not None or lin.layout in ("qkv", "silu") or getattr(lin, "norm_in", False) else {})
         for M in ms:
             x = torch.rand(M, lin.K, device=dev, generator=g).bfloat16()
             out = torch.empty(M, lin.N, dtype=torch.bfloat16, device=dev)
