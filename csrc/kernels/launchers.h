@@ -117,6 +117,10 @@ struct GemmArgs {
   void* fa_gran = nullptr;      // zeroed granule buffer (QaSync::gran), fa_gran_bytes long
   size_t fa_gran_bytes = 0;
   bool* fa_done = nullptr;
+  // FP8 W8A16 (gemm_fp8.hip): wp = e4m3fn codes [N/16][K/64][64][16 B], fp32 scales [fp8_groups][N] in the
+  // packed row order, fp8_groups = 1 (per channel) or K / 128 (block scales)
+  const float* fp8_scales = nullptr;
+  int fp8_groups = 0;
 };
 void launch_gemm(const GemmArgs& g, hipStream_t st);
 // stream-K decode GEMM (gemm_streamk.hip): M <= 16 dense rows, one equal share of the packed weight
@@ -136,6 +140,12 @@ bool launch_dense_kx(const GemmArgs& g, hipStream_t st);
 // AWQ W4A16 medium-M kernel (gemm_awq_mid.hip, 16 < M <= 64): g.waves tiles per block (8: one block
 // per CU owning whole tiles), g.splitk K slices; false for a shape / mode it does not take
 bool launch_awq_mid(const GemmArgs& g, hipStream_t st);
+// FP8 W8A16 decode GEMM (gemm_fp8.hip, M <= 16, K % 128 == 0): false for a mode it does not take (row
+// gather, folded-gamma row scale, fused all-reduce, fused attention, either side of the norm hand-off)
+bool launch_fp8_gemm(const GemmArgs& g, hipStream_t st);
+// e4m3 fragments -> bf16 fragment-packed copy (optionally gamma-folded) for the M > 16 bf16 kernels
+void launch_fp8_dequant(const void* wq, const float* scales, int groups, const uint16_t* gamma, void* out, int N,
+                        int K, hipStream_t st);
 // AWQ int4 fragments -> bf16 fragment-packed copy (optionally gamma-folded) for the prefill kernel
 void launch_awq_dequant(const void* wq, const uint16_t* scales, const uint16_t* sz, const uint16_t* gamma,
                         void* out, int N, int K, int group, hipStream_t st);

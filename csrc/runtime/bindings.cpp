@@ -130,7 +130,7 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
           const c10::optional<Tensor>& fa_out, const c10::optional<Tensor>& fa_part_o,
           const c10::optional<Tensor>& fa_part_ml, const c10::optional<Tensor>& fa_tickets,
           const c10::optional<Tensor>& fa_sync, int64_t fa_part_size, double fa_scale,
-          const c10::optional<Tensor>& fa_dbg_ts) {
+          const c10::optional<Tensor>& fa_dbg_ts, const c10::optional<Tensor>& fp8_scales) {
   CHECK_DEV(x); CHECK_DEV(wp); CHECK_DEV(out);
   CHECK_DT(x, torch::kBFloat16);
   CHECK_LASTDIM(x); CHECK_LASTDIM(out);
@@ -138,7 +138,27 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
   TORCH_CHECK(K % 32 == 0 && N % 16 == 0, "gemm: K%32 / N%16");
   TORCH_CHECK(x.size(1) >= K, "gemm: x has ", x.size(1), " cols < K=", K);
   const bool awq = awq_scales.has_value() && awq_scales->defined();
-  if (awq) {
+  const bool fp8 = fp8_scales.has_value() && fp8_scales->defined();
+  TORCH_CHECK(!(awq && fp8), "gemm: awq_scales and fp8_scales are exclusive");
+  if (fp8) {
+    // FP8 W8A16 decode kernel (gemm_fp8.hip): e4m3fn codes [N/16][K/64][64][16 B], fp32 scales [1][N] or [K/128][N]
+    CHECK_DT(wp, torch::kUInt8);
+    CHECK_DEV(*fp8_scales); CHECK_DT(*fp8_scales, torch::kFloat32);
+    TORCH_CHECK(N % 16 == 0 && K % 128 == 0, "fp8: N % 16 / K % 128");
+    TORCH_CHECK(wp.numel() == N * K && wp.is_contiguous(), "fp8: packed codes numel");
+    TORCH_CHECK(fp8_scales->dim() == 2 && fp8_scales->is_contiguous() && fp8_scales->size(1) == N &&
+                    (fp8_scales->size(0) == 1 || fp8_scales->size(0) == K / 128) &&
+                    reinterpret_cast<uintptr_t>(fp8_scales->data_ptr()) % 16 == 0,
+                "fp8: scales must be fp32 [1][N] or [K/128][N], 16-B aligned");
+    TORCH_CHECK(x.size(0) <= 16, "fp8: the decode kernel takes M <= 16 (longer steps: fp8_dequant + the bf16 kernels)");
+    TORCH_CHECK(!(row_idx.has_value() && row_idx->defined()), "fp8: row_idx is not taken");
+    TORCH_CHECK(!rownorm, "fp8: the folded-gamma row scale is not taken (pass norm_w)");
+    TORCH_CHECK(ar_bases.empty(), "fp8: the all-reduce epilogue is not taken");
+    TORCH_CHECK(!(fa_out.has_value() && fa_out->defined()), "fp8: fused-attention operands are not taken");
+    TORCH_CHECK(!(ssp_out.has_value() && ssp_out->defined()) && !(hg_out.has_value() && hg_out->defined()) &&
+                    !(ssp_in.has_value() && ssp_in->defined()),
+                "fp8: the norm hand-off is not taken in either direction");
+  } else if (awq) {
     CHECK_DT(wp, torch::kInt32);
     TORCH_CHECK(K % 128 == 0 && K % group == 0 && group % 32 == 0, "awq: K/group");
     TORCH_CHECK(wp.numel() == N * K / 8, "awq: packed qweight numel");
@@ -270,6 +290,12 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
     g.fa_done = &fa_done;
   }
   c10::DeviceGuard guard(x.device());
+  if (fp8) {
+    g.fp8_scales = reinterpret_cast<const float*>(fp8_scales->data_ptr());
+    g.fp8_groups = (int)fp8_scales->size(0);
+    TORCH_CHECK(vgate::launch_fp8_gemm(g, cur_stream()), "fp8: the decode kernel declined the call");
+    return;
+  }
   if (awq) vgate::launch_awq_gemm(g, cur_stream());
   else vgate::launch_gemm(g, cur_stream());
   if (fused_attn && !fa_done) vgate::launch_attention(fa, fa.S, cur_stream());
@@ -289,6 +315,24 @@ void awq_dequant(const Tensor& wq, const Tensor& scales, const Tensor& sz, int64
   c10::DeviceGuard guard(wq.device());
   vgate::launch_awq_dequant(wq.data_ptr(), bf16p(scales), bf16p(sz), g, out.data_ptr(), (int)N, (int)K, (int)group,
                             cur_stream());
+}
+
+// FP8 e4m3fn packed codes -> bf16 packed weight (same row order; optional gamma fold)
+void fp8_dequant(const Tensor& wq, const Tensor& scales, int64_t N, int64_t K, Tensor& out,
+                 const c10::optional<Tensor>& gamma) {
+  CHECK_DEV(wq); CHECK_DEV(scales); CHECK_DEV(out);
+  CHECK_DT(wq, torch::kUInt8); CHECK_DT(scales, torch::kFloat32); CHECK_DT(out, torch::kBFloat16);
+  TORCH_CHECK(N % 16 == 0 && K % 128 == 0, "fp8_dequant: N % 16 / K % 128");
+  TORCH_CHECK(wq.numel() == N * K && wq.is_contiguous() && out.numel() >= N * K && out.is_contiguous(),
+              "fp8_dequant: sizes");
+  TORCH_CHECK(scales.dim() == 2 && scales.is_contiguous() && scales.size(1) == N &&
+                  (scales.size(0) == 1 || scales.size(0) == K / 128),
+              "fp8_dequant: scales must be fp32 [1][N] or [K/128][N]");
+  const uint16_t* g = opt_bf16(gamma);
+  if (g) TORCH_CHECK(gamma->numel() == K && gamma->is_contiguous(), "fp8_dequant: gamma has K elements");
+  c10::DeviceGuard guard(wq.device());
+  vgate::launch_fp8_dequant(wq.data_ptr(), reinterpret_cast<const float*>(scales.data_ptr()), (int)scales.size(0), g,
+                            out.data_ptr(), (int)N, (int)K, cur_stream());
 }
 
 // y = rmsnorm(x [+ res]) * w ; res (if given) is updated in place to x + res
@@ -712,7 +756,7 @@ void custom_allgather(const Tensor& inp, Tensor& out, const std::vector<int64_t>
 PYBIND11_MODULE(_C, m) {
   m.doc() = "vgate gfx950 (MI355X) HIP kernels and native runtime";
   namespace py = pybind11;
-  m.def("gemm", &gemm, "fragment-packed MFMA GEMM (+RMSNorm prologue, split-K, fused epilogues; bf16 or AWQ int4)",
+  m.def("gemm", &gemm, "fragment-packed MFMA GEMM (+RMSNorm prologue, split-K, fused epilogues; bf16, AWQ int4 or FP8 e4m3)",
         py::arg("x"), py::arg("wp"), py::arg("N"), py::arg("K"), py::arg("out"), py::arg("epi") = 0,
         py::arg("bias") = py::none(), py::arg("res") = py::none(), py::arg("norm_w") = py::none(),
         py::arg("eps") = 1e-6, py::arg("row_idx") = py::none(), py::arg("ws") = py::none(),
@@ -727,7 +771,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ar_fused_off") = 0, py::arg("fa_block_tables") = py::none(), py::arg("fa_context_lens") = py::none(),
         py::arg("fa_query_start") = py::none(), py::arg("fa_out") = py::none(), py::arg("fa_part_o") = py::none(),
         py::arg("fa_part_ml") = py::none(), py::arg("fa_tickets") = py::none(), py::arg("fa_sync") = py::none(),
-        py::arg("fa_part_size") = 512, py::arg("fa_scale") = 1.0, py::arg("fa_dbg_ts") = py::none());
+        py::arg("fa_part_size") = 512, py::arg("fa_scale") = 1.0, py::arg("fa_dbg_ts") = py::none(),
+        py::arg("fp8_scales") = py::none());
   m.def("attention", &attention, "unified paged attention: decode (partitions merged in-launch) + varlen prefill tiles",
         py::arg("q"), py::arg("q_stride"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
         py::arg("context_lens"), py::arg("query_start"), py::arg("tile_seq"), py::arg("tile_q0"), py::arg("out"),
@@ -748,6 +793,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("awq_dequant", &awq_dequant, "AWQ int4 packed -> bf16 fragment-packed (prefill operand; optional gamma fold)",
         py::arg("wq"), py::arg("scales"), py::arg("sz"), py::arg("N"), py::arg("K"), py::arg("group"), py::arg("out"),
         py::arg("gamma") = py::none());
+  m.def("fp8_dequant", &fp8_dequant, "FP8 e4m3fn packed -> bf16 fragment-packed (M > 16 operand; optional gamma fold)",
+        py::arg("wq"), py::arg("scales"), py::arg("N"), py::arg("K"), py::arg("out"), py::arg("gamma") = py::none());
   m.def("silu_mul", &silu_mul, "out = silu(y[:, :I]) * y[:, I:] (library gate_up epilogue)");
   m.def("attn_decode", &attn_decode, "paged split-K decode attention");
   m.def("attn_prefill", &attn_prefill, "paged varlen causal prefill attention",

@@ -163,8 +163,8 @@ class ModelConfig(_Section):
         if v in (None, "", "none", "None"):
             return None
         v = str(v).lower()
-        if v not in ("awq",):
-            raise ValueError(f"unsupported quantization {v!r} (supported: awq)")
+        if v not in ("awq", "fp8"):
+            raise ValueError(f"unsupported quantization {v!r} (supported: awq, fp8)")
         return v
 
     @field_validator("kv_block_size")

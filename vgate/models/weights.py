@@ -3,7 +3,8 @@
 * ``random_init``: seeded random weights generated directly on the device in
   kernel-ready (fragment-packed) form — the benchmark path (no checkpoints
   exist on this machine). Scales keep activations O(1) so numerics are sane.
-* ``load_checkpoint``: HF safetensors (bf16/fp16/fp32 or AWQ int4 GEMM format),
+* ``load_checkpoint``: HF safetensors (bf16/fp16/fp32, AWQ int4 GEMM format or FP8 e4m3 with block /
+  per-channel / per-tensor weight scales),
   sharded for the model's TP rank at load time (only this rank's slices are
   materialised on the GPU).
 """
@@ -19,6 +20,8 @@ from vgate import ops
 from vgate.models.config import ModelArch
 
 AWQ_ORDER = [0, 2, 4, 6, 1, 3, 5, 7]  # AutoAWQ GEMM nibble order within an int32
+_FP8_DTYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz")
+                    if hasattr(torch, n))
 
 
 def _gen(device, seed):
@@ -55,6 +58,7 @@ def random_init(model, seed: int = 0) -> None:
     g = _gen(dev, seed * 1000003 + sh.tp.rank)
     H, D = a.hidden_size, a.head_dim
     awq = model.quant == "awq"
+    fp8 = model.quant == "fp8"
     group = 128
     model.embed = _randn((sh.vocab, H), 0.02, g, dev)
     layers = []
@@ -80,6 +84,11 @@ def random_init(model, seed: int = 0) -> None:
             o = ops.Linear(_randn((H, sh.hq * D), 1 / math.sqrt(sh.hq * D * sh.tp.size), g, dev))
             gu = ops.Linear(_randn((2 * sh.inter, H), 1 / math.sqrt(H), g, dev), kind="silu")
             down = ops.Linear(_randn((H, sh.inter), 1 / math.sqrt(sh.inter * sh.tp.size), g, dev))
+        if fp8:  # the dense branch's draws, quantized per output channel (embedding and LM head stay bf16)
+            qkv = ops.Linear.quantize_fp8(qkv.dense_weight(), bias=qkv_b, layout=qkv_layout)
+            o = ops.Linear.quantize_fp8(o.dense_weight())
+            gu = ops.Linear.quantize_fp8(gu.dense_weight(), layout="silu")
+            down = ops.Linear.quantize_fp8(down.dense_weight())
         qn, kn = (_rand_qk_norm(D, gn, dev), _rand_qk_norm(D, gn, dev)) if a.qk_norm else (None, None)
         layers.append(LayerWeights(
             in_norm=torch.ones(H, dtype=torch.bfloat16, device=dev), qkv=qkv, o=o,
@@ -159,7 +168,71 @@ def load_checkpoint(model, path: str) -> None:
     group = int(qcfg.get("group_size", 128))
 
     def dense(name: str) -> torch.Tensor:
-        return idx.get(name).to(torch.bfloat16)
+        t = idx.get(name)
+        if t.dtype in _FP8_DTYPES:
+            raise ValueError(f"{name}: {t.dtype} tensor where a bf16 / fp16 / fp32 one is expected")
+        return t.to(torch.bfloat16)
+
+    want_fp8 = model.quant == "fp8"
+    block = qcfg.get("weight_block_size")
+
+    def is_fp8(prefix: str) -> bool:
+        return idx.has(prefix + ".weight") and idx.get_slice(prefix + ".weight").get_dtype().upper().startswith("F8")
+
+    def fp8_parts(prefix: str, rows=None, ks=None):
+        """(codes uint8 [N, K], scales fp32 [G, N], G = 1 or K / 128) of an fp8 projection, restricted to
+        output rows [rows) or input columns [ks). The stored scale multiplies the code; activation
+        scales (input_scale) are ignored: W8A16."""
+        w = idx.get(prefix + ".weight")
+        if w.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"{prefix}.weight: {w.dtype} is not supported (FP8 weights must be float8_e4m3fn)")
+        N, K = w.shape
+        codes = w.view(torch.uint8)
+        if idx.has(prefix + ".weight_scale_inv"):
+            if block is None or list(block) != [128, 128]:
+                raise ValueError(f"{prefix}: block-scaled FP8 needs quantization_config.weight_block_size == "
+                                 f"[128, 128], got {block}")
+            s = idx.get(prefix + ".weight_scale_inv").float()
+            if tuple(s.shape) != ((N + 127) // 128, (K + 127) // 128) or K % 128:
+                raise ValueError(f"{prefix}.weight_scale_inv: shape {tuple(s.shape)} does not match 128 x 128 blocks "
+                                 f"of a [{N}, {K}] weight with K % 128 == 0")
+            scales = s.repeat_interleave(128, dim=0)[:N].t().contiguous()  # [K/128, N]
+        elif idx.has(prefix + ".weight_scale"):
+            s = idx.get(prefix + ".weight_scale").float()
+            if s.numel() == 1:
+                scales = s.reshape(1, 1).expand(1, N).contiguous()
+            elif s.numel() == N and s.dim() <= 2 and s.shape[0] == N:
+                scales = s.reshape(1, N).contiguous()
+            else:
+                raise ValueError(f"{prefix}.weight_scale: shape {tuple(s.shape)} is not [], [1], [N] or [N, 1]")
+        else:
+            raise ValueError(f"{prefix}: float8 weight without weight_scale_inv / weight_scale")
+        if rows is not None:
+            codes, scales = codes[rows[0]:rows[1]], scales[:, rows[0]:rows[1]]
+        if ks is not None:
+            if scales.shape[0] > 1:
+                if ks[0] % 128 or ks[1] % 128:
+                    raise ValueError(f"{prefix}: a TP shard's k-range [{ks[0]}, {ks[1]}) must be a multiple of the "
+                                     f"128-wide scale blocks")
+                scales = scales[ks[0] // 128: ks[1] // 128]
+            codes = codes[:, ks[0]:ks[1]]
+        return codes.contiguous(), scales.contiguous()
+
+    def make_fp8(parts, layout="plain", bias=None):
+        """One Linear from the row-wise concatenation of (codes, scales) parts."""
+        K = parts[0][0].shape[1]
+        if K % 128:
+            raise ValueError(f"FP8 Linear: K = {K} of this rank's shard is not a multiple of 128")
+        G = max(s.shape[0] for _, s in parts)
+        codes = torch.cat([c for c, _ in parts])
+        scales = torch.cat([s.expand(G, -1) if s.shape[0] != G else s for _, s in parts], dim=1)
+        return ops.Linear(None, bias, fp8={"codes": codes, "scales": scales.contiguous().to(dev), "layout": layout})
+
+    def maybe_fp8(w: torch.Tensor, **kw):
+        """A dense matrix of this rank: bf16 Linear, or quantized at load under ``quantization: fp8``."""
+        if want_fp8:
+            return ops.Linear.quantize_fp8(w.to(dev), **kw)
+        return ops.Linear(w.to(dev), **kw)
 
     def is_awq(prefix: str) -> bool:
         return idx.has(prefix + ".qweight")
@@ -209,16 +282,25 @@ def load_checkpoint(model, path: str) -> None:
             gu = make_awq((torch.cat([g_[0], u_[0]]), torch.cat([g_[1], u_[1]], 1), torch.cat([g_[2], u_[2]], 1)),
                           silu=True)
             down = make_awq(awq_cols(mlp + ".down_proj", sh.inter0, sh.inter0 + sh.inter))
+        elif is_fp8(att + ".q_proj"):
+            qkv = make_fp8([fp8_parts(att + ".q_proj", rows=(qa, qb)),
+                            fp8_parts(att + ".k_proj", rows=(ka - a.q_size, kb - a.q_size)),
+                            fp8_parts(att + ".v_proj", rows=(va - a.q_size - a.kv_size, vb - a.q_size - a.kv_size))],
+                           layout=qkv_layout, bias=bias)
+            o = make_fp8([fp8_parts(att + ".o_proj", ks=(qa, qb))])
+            gu = make_fp8([fp8_parts(mlp + ".gate_proj", rows=(sh.inter0, sh.inter0 + sh.inter)),
+                           fp8_parts(mlp + ".up_proj", rows=(sh.inter0, sh.inter0 + sh.inter))], layout="silu")
+            down = make_fp8([fp8_parts(mlp + ".down_proj", ks=(sh.inter0, sh.inter0 + sh.inter))])
         else:
             wq = dense(att + ".q_proj.weight")[qa:qb]
             wk = dense(att + ".k_proj.weight")[ka - a.q_size: kb - a.q_size]
             wv = dense(att + ".v_proj.weight")[va - a.q_size - a.kv_size: vb - a.q_size - a.kv_size]
-            qkv = ops.Linear(torch.cat([wq, wk, wv]).to(dev), bias=bias, layout=qkv_layout)
-            o = ops.Linear(dense(att + ".o_proj.weight")[:, qa:qb].contiguous().to(dev))
+            qkv = maybe_fp8(torch.cat([wq, wk, wv]), bias=bias, layout=qkv_layout)
+            o = maybe_fp8(dense(att + ".o_proj.weight")[:, qa:qb].contiguous())
             wg = dense(mlp + ".gate_proj.weight")[sh.inter0: sh.inter0 + sh.inter]
             wu = dense(mlp + ".up_proj.weight")[sh.inter0: sh.inter0 + sh.inter]
-            gu = ops.Linear(torch.cat([wg, wu]).to(dev), kind="silu")
-            down = ops.Linear(dense(mlp + ".down_proj.weight")[:, sh.inter0: sh.inter0 + sh.inter].contiguous().to(dev))
+            gu = maybe_fp8(torch.cat([wg, wu]), layout="silu")
+            down = maybe_fp8(dense(mlp + ".down_proj.weight")[:, sh.inter0: sh.inter0 + sh.inter].contiguous())
         qn = kn = None
         if a.qk_norm:  # [head_dim] each, shared by every head: replicated on every TP rank
             missing = [k for k in (att + ".q_norm.weight", att + ".k_norm.weight") if not idx.has(k)]

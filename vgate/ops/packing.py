@@ -64,6 +64,30 @@ def pack_awq_sz(scales: torch.Tensor, sz: torch.Tensor) -> torch.Tensor:
     return torch.cat([s4, z4], dim=-1).to(torch.bfloat16).contiguous()  # [nt][g][4][8]
 
 
+def pack_fp8(codes: torch.Tensor) -> torch.Tensor:
+    """e4m3fn codes uint8 [N, K] -> uint8 [N/16, K/64, 64, 16]: byte 8u + j of lane l is the code of
+    W[16nt + (l&15)][64kp + 32u + 8(l>>4) + j], u = 0, 1, j = 0..7, so one 16-B lane load is the A
+    operand of two MFMA k-steps (csrc/kernels/gemm_fp8.hip)."""
+    N, K = codes.shape
+    assert codes.dtype == torch.uint8 and N % 16 == 0 and K % 64 == 0, (codes.dtype, N, K)
+    c = codes.reshape(N // 16, 16, K // 64, 2, 4, 8)  # nt, r, kp, u, g, j
+    return c.permute(0, 2, 4, 1, 3, 5).reshape(N // 16, K // 64, 64, 16).contiguous()  # lane = g * 16 + r
+
+
+def unpack_fp8(packed: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of :func:`pack_fp8`: uint8 [N/16, K/64, 64, 16] -> codes uint8 [N, K]."""
+    c = packed.reshape(N // 16, K // 64, 4, 16, 2, 8)  # nt, kp, g, r, u, j
+    return c.permute(0, 3, 1, 4, 2, 5).reshape(N, K)
+
+
+def fp8_dequant_ref(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """bf16(fp32(code) * scale): codes uint8 [N, K] (e4m3fn), scales fp32 [G, N], G = 1 or K / 128."""
+    N, K = codes.shape
+    G = scales.shape[0]
+    g = torch.arange(K, device=codes.device) // (K // G)
+    return (codes.view(torch.float8_e4m3fn).float() * scales.float()[g].t()).to(torch.bfloat16)
+
+
 def row_permutation(N: int, layout: str) -> torch.Tensor | None:
     """Row order of the packed weight for a fused epilogue (None = identity).
 
@@ -93,18 +117,21 @@ class Linear:
 
     layout: "plain" | "silu" (rows [gate; up] -> out = silu(gate) * up)
             | "qkv" (rows [q; k; v], heads of 128: fused bias + RoPE + KV-cache write).
-    Dense bf16 weights or AWQ int4 (``awq={"qint", "scales", "zeros", "group"}``).
+    Dense bf16 weights, AWQ int4 (``awq={"qint", "scales", "zeros", "group"}``) or FP8 W8A16
+    (``fp8={"codes", "scales", "layout"}``: e4m3fn codes uint8 [N, K], fp32 scales [1, N] per channel or
+    [K/128, N] per 128-k block, original row order; the weight is code * scale).
     On GPU only the fragment-packed copy is kept; on CPU the dense matrix (reference path).
     """
 
     def __init__(self, w: torch.Tensor | None, bias: torch.Tensor | None = None, kind: str = "plain",
-                 awq: dict | None = None, layout: str | None = None):
+                 awq: dict | None = None, layout: str | None = None, fp8: dict | None = None):
         if kind in ("silu", "qkv"):
             layout, kind = kind, "dense"
-        self.layout = layout or (awq.get("layout", "plain") if awq else "plain")
+        quant = awq if awq is not None else fp8
+        self.layout = layout or (quant.get("layout", "plain") if quant else "plain")
         if awq is not None and awq.get("silu"):
             self.layout = "silu"
-        self.kind = "awq" if awq is not None else "dense"
+        self.kind = "awq" if awq is not None else "fp8" if fp8 is not None else "dense"
         self.bias = bias
         self.norm_gamma = None  # RMSNorm weight folded into the packed copy (see fold_norm)
         # a plain-layout Linear whose input is RMSNormed in its launch (a QK-norm model's QKV projection;
@@ -122,6 +149,30 @@ class Linear:
         self.prefill_plan: dict[int, tuple[int, int]] = {}
         self.w = self.wp = None  # the dense matrix on the CPU, the packed copy on a GPU
         self.szp = None  # AWQ group 128 on a GPU: the packed (scale, scale * zero) operand (pack_awq_sz)
+        self.fscales = None  # FP8 on a GPU: fp32 scales [G, N] in the packed row order
+        if self.kind == "fp8":
+            codes, scales = fp8["codes"], fp8["scales"]
+            if codes.dtype == torch.float8_e4m3fn:
+                codes = codes.view(torch.uint8)
+            self.N, self.K = codes.shape
+            if codes.dtype != torch.uint8 or self.N % 16 or self.K % 128:
+                raise ValueError(f"fp8 Linear: e4m3fn codes [N % 16 == 0, K % 128 == 0], got {codes.dtype} "
+                                 f"{tuple(codes.shape)}")
+            if scales.dim() != 2 or scales.shape[1] != self.N or scales.shape[0] not in (1, self.K // 128):
+                raise ValueError(f"fp8 Linear: scales [1, N] or [K/128, N], got {tuple(scales.shape)}")
+            dev = scales.device
+            scales = scales.to(torch.float32)
+            if dev.type == "cuda":
+                codes = codes.to(dev)
+                perm = row_permutation(self.N, self.layout)
+                if perm is not None:
+                    pd = perm.to(dev)
+                    codes, scales = codes[pd], scales[:, pd]
+                self.wp = pack_fp8(codes.contiguous())
+                self.fscales = scales.contiguous()
+            else:
+                self.w = fp8_dequant_ref(codes, scales)
+            return
         if self.kind == "awq":
             q = awq["qint"]
             self.N, self.K = q.shape
@@ -148,6 +199,16 @@ class Linear:
             self.wp = pack_weight(w[perm.to(w.device)] if perm is not None else w)
         else:
             self.w = w
+
+    @classmethod
+    def quantize_fp8(cls, w: torch.Tensor, bias: torch.Tensor | None = None, layout: str = "plain") -> "Linear":
+        """Load-time per-output-channel FP8 quantization of a bf16 matrix [N, K]: s = amax_row / 448 (1 for
+        an all-zero row), code = (w / s) rounded to e4m3fn."""
+        wf = w.float()
+        amax = wf.abs().amax(dim=1)
+        s = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+        codes = (wf / s[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+        return cls(None, bias, fp8={"codes": codes, "scales": s[None].contiguous(), "layout": layout})
 
     def fold_norm(self, gamma: torch.Tensor) -> bool:
         """Fold the preceding RMSNorm's weight into the packed matrix: W'[n,k] = W[n,k]*g[k].
@@ -184,6 +245,8 @@ class Linear:
             g = torch.arange(self.K, device=q.device) // self.group
             w = (q.float() * self.scales.float()[g].t() - self.zeros.float()[g].t()).to(torch.bfloat16)
             return self._original_rows(w)
+        if self.kind == "fp8":  # bf16(code * scale), the CPU Linear's matrix
+            return self._original_rows(fp8_dequant_ref(unpack_fp8(self.wp, self.N, self.K), self.fscales))
         w = unpack_weight(self.wp, self.N, self.K)
         if self.norm_gamma is not None:  # un-fold (approximate: W' was rounded to bf16)
             w = (w.float() / self.norm_gamma.to(w.device, torch.float32)[None]).to(torch.bfloat16)
@@ -194,6 +257,8 @@ class Linear:
         if self.kind == "awq" and self.w is None:
             n = self.wp.numel() * 4 + self.scales.numel() * 4  # int4 + (s, s*z) bf16 per group
             return n + (self.szp.numel() * 2 if self.szp is not None else 0)
+        if self.kind == "fp8" and self.w is None:
+            return self.wp.numel() + self.fscales.numel() * 4  # codes + fp32 scales
         t = self.wp if self.wp is not None else self.w
         return t.numel() * t.element_size()
 
