@@ -121,6 +121,9 @@ struct GemmArgs {
   // packed row order, fp8_groups = 1 (per channel) or K / 128 (block scales)
   const float* fp8_scales = nullptr;
   int fp8_groups = 0;
+  // MXFP4 W4A16 (gemm_mxfp4.hip): wp = e2m1 codes [N/16][K/128][64][16 B], e8m0 scale bytes
+  // [N/16][K/128][16 rows][4 B] in the packed row order (byte u: k-step 4 kq + u)
+  const void* mxfp4_scales = nullptr;
 };
 void launch_gemm(const GemmArgs& g, hipStream_t st);
 // stream-K decode GEMM (gemm_streamk.hip): M <= 16 dense rows, one equal share of the packed weight
@@ -146,6 +149,12 @@ bool launch_fp8_gemm(const GemmArgs& g, hipStream_t st);
 // e4m3 fragments -> bf16 fragment-packed copy (optionally gamma-folded) for the M > 16 bf16 kernels
 void launch_fp8_dequant(const void* wq, const float* scales, int groups, const uint16_t* gamma, void* out, int N,
                         int K, hipStream_t st);
+// MXFP4 W4A16 decode GEMM (gemm_mxfp4.hip, M <= 16, K % 128 == 0): false for a mode it does not take (as
+// launch_fp8_gemm)
+bool launch_mxfp4_gemm(const GemmArgs& g, hipStream_t st);
+// e2m1 fragments + e8m0 scales -> bf16 fragment-packed copy (optionally gamma-folded) for the M > 16 bf16 kernels
+void launch_mxfp4_dequant(const void* wq, const void* sq, const uint16_t* gamma, void* out, int N, int K,
+                          hipStream_t st);
 // AWQ int4 fragments -> bf16 fragment-packed copy (optionally gamma-folded) for the prefill kernel
 void launch_awq_dequant(const void* wq, const uint16_t* scales, const uint16_t* sz, const uint16_t* gamma,
                         void* out, int N, int K, int group, hipStream_t st);

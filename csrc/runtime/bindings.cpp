@@ -130,7 +130,8 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
           const c10::optional<Tensor>& fa_out, const c10::optional<Tensor>& fa_part_o,
           const c10::optional<Tensor>& fa_part_ml, const c10::optional<Tensor>& fa_tickets,
           const c10::optional<Tensor>& fa_sync, int64_t fa_part_size, double fa_scale,
-          const c10::optional<Tensor>& fa_dbg_ts, const c10::optional<Tensor>& fp8_scales) {
+          const c10::optional<Tensor>& fa_dbg_ts, const c10::optional<Tensor>& fp8_scales,
+          const c10::optional<Tensor>& mxfp4_scales) {
   CHECK_DEV(x); CHECK_DEV(wp); CHECK_DEV(out);
   CHECK_DT(x, torch::kBFloat16);
   CHECK_LASTDIM(x); CHECK_LASTDIM(out);
@@ -139,8 +140,27 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
   TORCH_CHECK(x.size(1) >= K, "gemm: x has ", x.size(1), " cols < K=", K);
   const bool awq = awq_scales.has_value() && awq_scales->defined();
   const bool fp8 = fp8_scales.has_value() && fp8_scales->defined();
-  TORCH_CHECK(!(awq && fp8), "gemm: awq_scales and fp8_scales are exclusive");
-  if (fp8) {
+  const bool mxfp4 = mxfp4_scales.has_value() && mxfp4_scales->defined();
+  TORCH_CHECK(!(awq && fp8) && !(mxfp4 && (awq || fp8)), "gemm: awq_scales, fp8_scales and mxfp4_scales are exclusive");
+  if (mxfp4) {
+    // MXFP4 W4A16 decode kernel (gemm_mxfp4.hip): e2m1 codes [N/16][K/128][64][16 B], e8m0 bytes [N/16][K/128][16][4]
+    CHECK_DT(wp, torch::kUInt8);
+    CHECK_DEV(*mxfp4_scales); CHECK_DT(*mxfp4_scales, torch::kUInt8);
+    TORCH_CHECK(N % 16 == 0 && K % 128 == 0, "mxfp4: N % 16 / K % 128");
+    TORCH_CHECK(wp.numel() == N * K / 2 && wp.is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(wp.data_ptr()) % 16 == 0, "mxfp4: packed codes numel");
+    TORCH_CHECK(mxfp4_scales->numel() == N * K / 32 && mxfp4_scales->is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(mxfp4_scales->data_ptr()) % 4 == 0,
+                "mxfp4: scales must be uint8 [N/16][K/128][16][4], 4-B aligned");
+    TORCH_CHECK(x.size(0) <= 16, "mxfp4: the decode kernel takes M <= 16 (longer steps: mxfp4_dequant + the bf16 kernels)");
+    TORCH_CHECK(!(row_idx.has_value() && row_idx->defined()), "mxfp4: row_idx is not taken");
+    TORCH_CHECK(!rownorm, "mxfp4: the folded-gamma row scale is not taken (pass norm_w)");
+    TORCH_CHECK(ar_bases.empty(), "mxfp4: the all-reduce epilogue is not taken");
+    TORCH_CHECK(!(fa_out.has_value() && fa_out->defined()), "mxfp4: fused-attention operands are not taken");
+    TORCH_CHECK(!(ssp_out.has_value() && ssp_out->defined()) && !(hg_out.has_value() && hg_out->defined()) &&
+                    !(ssp_in.has_value() && ssp_in->defined()),
+                "mxfp4: the norm hand-off is not taken in either direction");
+  } else if (fp8) {
     // FP8 W8A16 decode kernel (gemm_fp8.hip): e4m3fn codes [N/16][K/64][64][16 B], fp32 scales [1][N] or [K/128][N]
     CHECK_DT(wp, torch::kUInt8);
     CHECK_DEV(*fp8_scales); CHECK_DT(*fp8_scales, torch::kFloat32);
@@ -296,6 +316,11 @@ void gemm(const Tensor& x, const Tensor& wp, int64_t N, int64_t K, Tensor& out, 
     TORCH_CHECK(vgate::launch_fp8_gemm(g, cur_stream()), "fp8: the decode kernel declined the call");
     return;
   }
+  if (mxfp4) {
+    g.mxfp4_scales = mxfp4_scales->data_ptr();
+    TORCH_CHECK(vgate::launch_mxfp4_gemm(g, cur_stream()), "mxfp4: the decode kernel declined the call");
+    return;
+  }
   if (awq) vgate::launch_awq_gemm(g, cur_stream());
   else vgate::launch_gemm(g, cur_stream());
   if (fused_attn && !fa_done) vgate::launch_attention(fa, fa.S, cur_stream());
@@ -333,6 +358,25 @@ void fp8_dequant(const Tensor& wq, const Tensor& scales, int64_t N, int64_t K, T
   c10::DeviceGuard guard(wq.device());
   vgate::launch_fp8_dequant(wq.data_ptr(), reinterpret_cast<const float*>(scales.data_ptr()), (int)scales.size(0), g,
                             out.data_ptr(), (int)N, (int)K, cur_stream());
+}
+
+// MXFP4 packed e2m1 codes + e8m0 scales -> bf16 packed weight (same row order; optional gamma fold)
+void mxfp4_dequant(const Tensor& wq, const Tensor& scales, int64_t N, int64_t K, Tensor& out,
+                   const c10::optional<Tensor>& gamma) {
+  CHECK_DEV(wq); CHECK_DEV(scales); CHECK_DEV(out);
+  CHECK_DT(wq, torch::kUInt8); CHECK_DT(scales, torch::kUInt8); CHECK_DT(out, torch::kBFloat16);
+  TORCH_CHECK(N % 16 == 0 && K % 128 == 0, "mxfp4_dequant: N % 16 / K % 128");
+  TORCH_CHECK(wq.numel() == N * K / 2 && wq.is_contiguous() && out.numel() >= N * K && out.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "mxfp4_dequant: sizes");
+  TORCH_CHECK(scales.numel() == N * K / 32 && scales.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              "mxfp4_dequant: scales must be uint8 [N/16][K/128][16][4]");
+  const uint16_t* g = opt_bf16(gamma);
+  if (g) TORCH_CHECK(gamma->numel() == K && gamma->is_contiguous(), "mxfp4_dequant: gamma has K elements");
+  c10::DeviceGuard guard(wq.device());
+  vgate::launch_mxfp4_dequant(wq.data_ptr(), scales.data_ptr(), g, out.data_ptr(), (int)N, (int)K, cur_stream());
 }
 
 // y = rmsnorm(x [+ res]) * w ; res (if given) is updated in place to x + res
@@ -756,7 +800,7 @@ void custom_allgather(const Tensor& inp, Tensor& out, const std::vector<int64_t>
 PYBIND11_MODULE(_C, m) {
   m.doc() = "vgate gfx950 (MI355X) HIP kernels and native runtime";
   namespace py = pybind11;
-  m.def("gemm", &gemm, "fragment-packed MFMA GEMM (+RMSNorm prologue, split-K, fused epilogues; bf16, AWQ int4 or FP8 e4m3)",
+  m.def("gemm", &gemm, "fragment-packed MFMA GEMM (+RMSNorm prologue, split-K, fused epilogues; bf16, AWQ int4, FP8 e4m3 or MXFP4 e2m1)",
         py::arg("x"), py::arg("wp"), py::arg("N"), py::arg("K"), py::arg("out"), py::arg("epi") = 0,
         py::arg("bias") = py::none(), py::arg("res") = py::none(), py::arg("norm_w") = py::none(),
         py::arg("eps") = 1e-6, py::arg("row_idx") = py::none(), py::arg("ws") = py::none(),
@@ -772,7 +816,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("fa_query_start") = py::none(), py::arg("fa_out") = py::none(), py::arg("fa_part_o") = py::none(),
         py::arg("fa_part_ml") = py::none(), py::arg("fa_tickets") = py::none(), py::arg("fa_sync") = py::none(),
         py::arg("fa_part_size") = 512, py::arg("fa_scale") = 1.0, py::arg("fa_dbg_ts") = py::none(),
-        py::arg("fp8_scales") = py::none());
+        py::arg("fp8_scales") = py::none(), py::arg("mxfp4_scales") = py::none());
   m.def("attention", &attention, "unified paged attention: decode (partitions merged in-launch) + varlen prefill tiles",
         py::arg("q"), py::arg("q_stride"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
         py::arg("context_lens"), py::arg("query_start"), py::arg("tile_seq"), py::arg("tile_q0"), py::arg("out"),
@@ -794,6 +838,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wq"), py::arg("scales"), py::arg("sz"), py::arg("N"), py::arg("K"), py::arg("group"), py::arg("out"),
         py::arg("gamma") = py::none());
   m.def("fp8_dequant", &fp8_dequant, "FP8 e4m3fn packed -> bf16 fragment-packed (M > 16 operand; optional gamma fold)",
+        py::arg("wq"), py::arg("scales"), py::arg("N"), py::arg("K"), py::arg("out"), py::arg("gamma") = py::none());
+  m.def("mxfp4_dequant", &mxfp4_dequant, "MXFP4 e2m1 packed + e8m0 scales -> bf16 fragment-packed (M > 16 operand; optional gamma fold)",
         py::arg("wq"), py::arg("scales"), py::arg("N"), py::arg("K"), py::arg("out"), py::arg("gamma") = py::none());
   m.def("silu_mul", &silu_mul, "out = silu(y[:, :I]) * y[:, I:] (library gate_up epilogue)");
   m.def("attn_decode", &attn_decode, "paged split-K decode attention");

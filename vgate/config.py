@@ -163,8 +163,8 @@ class ModelConfig(_Section):
         if v in (None, "", "none", "None"):
             return None
         v = str(v).lower()
-        if v not in ("awq", "fp8"):
-            raise ValueError(f"unsupported quantization {v!r} (supported: awq, fp8)")
+        if v not in ("awq", "fp8", "mxfp4"):
+            raise ValueError(f"unsupported quantization {v!r} (supported: awq, fp8, mxfp4)")
         return v
 
     @field_validator("kv_block_size")

@@ -44,13 +44,33 @@ PLANS: dict[tuple[int, int, str, str], tuple] = {
     # profiles/r3_awq_decode_sweep.log)
 }
 
+# MXFP4 (csrc/kernels/gemm_mxfp4.hip): the same key and value forms as PLANS, in a table of its own (PLANS holds
+# the dense and AWQ kinds only). Unlike the entries above these come from the per-launch cold-weight
+# probe, not a whole-step sweep (benchmarks/probes/mxfp4_sweep.py --plan-sweep, profiles/mxfp4_plan_sweep.log;
+# us at M = 8, the launcher's own plan first): at 4 bits a wave's weight stream is a quarter of the bf16
+# one, so the large matrices want more K slices or tile groups in flight than the bf16 heuristic gives.
+# o_proj of both models and the Qwen qkv measured best on the heuristic.
+MXFP4_PLANS: dict[tuple[int, int, str, str], tuple] = {
+    (17920, 1536, "silu", "mxfp4"): (4, 1, 4),   # Qwen2.5-1.5B gate_up: 15.5 -> 14.5
+    (1536, 8960, "plain", "mxfp4"): (4, 4, 2),   # Qwen2.5-1.5B down: 13.4 -> 11.5 (M = 16: 17.2 -> 12.1)
+    (6144, 4096, "qkv", "mxfp4"): (4, 2, 1),     # Llama-3-8B qkv: 18.1 -> 15.7
+    (28672, 4096, "silu", "mxfp4"): (4, 1, 4),   # Llama-3-8B gate_up: 31.6 -> 24.4
+    (4096, 14336, "plain", "mxfp4"): (8, 4, 4),  # Llama-3-8B down: 17.4 -> 15.1 (M = 16: 22.8 -> 16.8; later runs 20.2 / 25.0: README "MXFP4")
+}
+
+
+def lookup(lin):
+    """The measured plan of one Linear, or None."""
+    key = (lin.N, lin.K, lin.layout, lin.kind)
+    return PLANS.get(key) or MXFP4_PLANS.get(key)
+
 
 def apply(model) -> int:
     """Set the measured plan on every Linear of ``model`` whose shape has one; returns how many."""
     n = 0
     lins = [lin for L in model.layers for lin in (L.qkv, L.o, L.gate_up, L.down)] + [model.lm_head]
     for lin in lins:
-        p = PLANS.get((lin.N, lin.K, lin.layout, lin.kind))
+        p = lookup(lin)
         if p is not None:
             if p[0] == "sk":
                 lin.dec_sk = tuple(p[1:])

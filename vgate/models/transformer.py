@@ -115,8 +115,8 @@ class DecoderModel:
                 if L.q_norm is None or L.k_norm is None or L.qkv.layout != "plain":
                     raise ValueError("qk_norm: every layer needs q_norm / k_norm and a plain-layout QKV projection")
                 L.qkv.norm_in = True
-        if self.device.type == "cuda" and self.quant in ("awq", "fp8"):
-            # long AWQ / FP8 steps: int4 / e4m3 -> bf16 dequant of one matrix at a time into a shared
+        if self.device.type == "cuda" and self.quant in ("awq", "fp8", "mxfp4"):
+            # long AWQ / FP8 / MXFP4 steps: int4 / e4m3 / e2m1 -> bf16 dequant of one matrix at a time into a shared
             # scratch (ops.linear), sized once here so graph capture never allocates
             lins = [lin for L in self.layers for lin in (L.qkv, L.o, L.gate_up, L.down)]
             ops.reserve_awq_scratch(self.device, max(lin.N * lin.K for lin in lins if lin.kind == self.quant))

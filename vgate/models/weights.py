@@ -3,8 +3,8 @@
 * ``random_init``: seeded random weights generated directly on the device in
   kernel-ready (fragment-packed) form — the benchmark path (no checkpoints
   exist on this machine). Scales keep activations O(1) so numerics are sane.
-* ``load_checkpoint``: HF safetensors (bf16/fp16/fp32, AWQ int4 GEMM format or FP8 e4m3 with block /
-  per-channel / per-tensor weight scales),
+* ``load_checkpoint``: HF safetensors (bf16/fp16/fp32, AWQ int4 GEMM format, FP8 e4m3 with block /
+  per-channel / per-tensor weight scales, or MXFP4: packed e2m1 nibbles with e8m0 block-32 scales),
   sharded for the model's TP rank at load time (only this rank's slices are
   materialised on the GPU).
 """
@@ -59,6 +59,7 @@ def random_init(model, seed: int = 0) -> None:
     H, D = a.hidden_size, a.head_dim
     awq = model.quant == "awq"
     fp8 = model.quant == "fp8"
+    mxfp4 = model.quant == "mxfp4"
     group = 128
     model.embed = _randn((sh.vocab, H), 0.02, g, dev)
     layers = []
@@ -89,6 +90,11 @@ def random_init(model, seed: int = 0) -> None:
             o = ops.Linear.quantize_fp8(o.dense_weight())
             gu = ops.Linear.quantize_fp8(gu.dense_weight(), layout="silu")
             down = ops.Linear.quantize_fp8(down.dense_weight())
+        if mxfp4:  # the dense branch's draws in OCP MX blocks of 32 (embedding and LM head stay bf16)
+            qkv = ops.Linear.quantize_mxfp4(qkv.dense_weight(), bias=qkv_b, layout=qkv_layout)
+            o = ops.Linear.quantize_mxfp4(o.dense_weight())
+            gu = ops.Linear.quantize_mxfp4(gu.dense_weight(), layout="silu")
+            down = ops.Linear.quantize_mxfp4(down.dense_weight())
         qn, kn = (_rand_qk_norm(D, gn, dev), _rand_qk_norm(D, gn, dev)) if a.qk_norm else (None, None)
         layers.append(LayerWeights(
             in_norm=torch.ones(H, dtype=torch.bfloat16, device=dev), qkv=qkv, o=o,
@@ -229,10 +235,58 @@ def load_checkpoint(model, path: str) -> None:
         return ops.Linear(None, bias, fp8={"codes": codes, "scales": scales.contiguous().to(dev), "layout": layout})
 
     def maybe_fp8(w: torch.Tensor, **kw):
-        """A dense matrix of this rank: bf16 Linear, or quantized at load under ``quantization: fp8``."""
+        """A dense matrix of this rank: bf16 Linear, or quantized at load under ``quantization: fp8`` /
+        ``quantization: mxfp4``."""
         if want_fp8:
             return ops.Linear.quantize_fp8(w.to(dev), **kw)
+        if model.quant == "mxfp4":
+            return ops.Linear.quantize_mxfp4(w.to(dev), **kw)
         return ops.Linear(w.to(dev), **kw)
+
+    def is_mxfp4(prefix: str) -> bool:
+        if not idx.has(prefix + ".weight"):
+            return False
+        dt = idx.get_slice(prefix + ".weight").get_dtype().upper()
+        return dt == "U8" or dt.startswith("F4")
+
+    def mxfp4_parts(prefix: str, rows=None, ks=None):
+        """(codes uint8 [N, K] one nibble value per byte, scales uint8 [N, K/32]) of an MXFP4 projection:
+        ``weight`` uint8 [N, K/2] with element 2i in the low nibble of byte i, ``weight_scale`` e8m0 bytes
+        [N, K/32]; restricted to output rows [rows) or input columns [ks). Scale bytes are validated here so
+        the message carries the tensor's name; activation-quantization entries (input_scale) are ignored: W4A16."""
+        w = idx.get(prefix + ".weight")
+        if w.dtype != torch.uint8:  # torch.float4_e2m1fn_x2, where the installed safetensors yields it
+            w = w.view(torch.uint8)
+        if w.dim() != 2:
+            raise ValueError(f"{prefix}.weight: MXFP4 codes must be [N, K/2], got {tuple(w.shape)}")
+        N, K = w.shape[0], 2 * w.shape[1]
+        if not idx.has(prefix + ".weight_scale"):
+            raise ValueError(f"{prefix}.weight: packed 4-bit weight without {prefix}.weight_scale")
+        s = idx.get(prefix + ".weight_scale")
+        if s.dtype != torch.uint8:
+            if s.element_size() != 1:
+                raise ValueError(f"{prefix}.weight_scale: {s.dtype} is not e8m0 (uint8 / float8_e8m0fnu)")
+            s = s.view(torch.uint8)
+        if K % 128:
+            raise ValueError(f"{prefix}.weight: K = {K} is not a multiple of 128")
+        if tuple(s.shape) != (N, K // 32):
+            raise ValueError(f"{prefix}.weight_scale: shape {tuple(s.shape)} does not match [N, K/32] = "
+                             f"[{N}, {K // 32}] of the weight")
+        codes = torch.stack([w & 0xF, w >> 4], dim=-1).reshape(N, K)
+        s = ops.packing.mxfp4_check_scales(codes, s, prefix + ".weight_scale")
+        if rows is not None:
+            codes, s = codes[rows[0]:rows[1]], s[rows[0]:rows[1]]
+        if ks is not None:
+            if ks[0] % 128 or ks[1] % 128:
+                raise ValueError(f"{prefix}.weight: a TP shard's k-range [{ks[0]}, {ks[1]}) must be a multiple of 128")
+            codes, s = codes[:, ks[0]:ks[1]], s[:, ks[0] // 32: ks[1] // 32]
+        return codes.contiguous(), s.contiguous()
+
+    def make_mxfp4(parts, layout="plain", bias=None):
+        """One Linear from the row-wise concatenation of (codes, scales) parts."""
+        codes = torch.cat([c for c, _ in parts])
+        scales = torch.cat([s_ for _, s_ in parts])
+        return ops.Linear(None, bias, mxfp4={"codes": codes, "scales": scales.to(dev), "layout": layout})
 
     def is_awq(prefix: str) -> bool:
         return idx.has(prefix + ".qweight")
@@ -282,6 +336,15 @@ def load_checkpoint(model, path: str) -> None:
             gu = make_awq((torch.cat([g_[0], u_[0]]), torch.cat([g_[1], u_[1]], 1), torch.cat([g_[2], u_[2]], 1)),
                           silu=True)
             down = make_awq(awq_cols(mlp + ".down_proj", sh.inter0, sh.inter0 + sh.inter))
+        elif is_mxfp4(att + ".q_proj"):
+            qkv = make_mxfp4([mxfp4_parts(att + ".q_proj", rows=(qa, qb)),
+                              mxfp4_parts(att + ".k_proj", rows=(ka - a.q_size, kb - a.q_size)),
+                              mxfp4_parts(att + ".v_proj", rows=(va - a.q_size - a.kv_size, vb - a.q_size - a.kv_size))],
+                             layout=qkv_layout, bias=bias)
+            o = make_mxfp4([mxfp4_parts(att + ".o_proj", ks=(qa, qb))])
+            gu = make_mxfp4([mxfp4_parts(mlp + ".gate_proj", rows=(sh.inter0, sh.inter0 + sh.inter)),
+                             mxfp4_parts(mlp + ".up_proj", rows=(sh.inter0, sh.inter0 + sh.inter))], layout="silu")
+            down = make_mxfp4([mxfp4_parts(mlp + ".down_proj", ks=(sh.inter0, sh.inter0 + sh.inter))])
         elif is_fp8(att + ".q_proj"):
             qkv = make_fp8([fp8_parts(att + ".q_proj", rows=(qa, qb)),
                             fp8_parts(att + ".k_proj", rows=(ka - a.q_size, kb - a.q_size)),

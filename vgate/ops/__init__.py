@@ -19,8 +19,9 @@ from ._native import (EPI_BF16, EPI_F32, EPI_QKV, EPI_SILU, PATH_AUTO, PATH_KX, 
                       PATH_STREAMK, native, native_available)
 from .buffers import (_TICKETS, _WS, attn_tickets, fault_word, logprob_partials, qa_sync,  # noqa: F401
                       reserve_awq_scratch, reset_handoffs, sample_workspace, sk_workspace, workspace)
-from .packing import (Linear, interleave_gate_up, pack_awq, pack_awq_sz, pack_fp8, pack_weight,  # noqa: F401
-                      row_permutation, unpack_awq, unpack_fp8, unpack_weight)
+from .packing import (Linear, interleave_gate_up, mxfp4_dequant_ref, pack_awq, pack_awq_sz, pack_fp8,  # noqa: F401
+                      pack_mxfp4, pack_mxfp4_scales, pack_weight, row_permutation, unpack_awq, unpack_fp8,
+                      unpack_mxfp4, unpack_mxfp4_scales, unpack_weight)
 from .tuner import (MEDIUM_DEFAULT, MID_BASE, MID_CANDIDATES, PREFILL_CANDIDATES,  # noqa: F401
                     PREFILL_RING_CANDIDATES, _cold_timer, _plan_bucket, _plan_kw, apply_prefill_plans,
                     load_plan_cache, save_plan_cache, tune_prefill, tune_prefill_cached)
@@ -63,11 +64,11 @@ def _gemm_route(lin: Linear, M: int, *, waves: int, splitk: int, path: int, row_
             return ("gemm", PATH_MID, 0, 0, 0)  # int4 medium kernel (gemm_awq_mid.hip awq_mid_kernel): no bf16 scratch
         if M >= AWQ_DEQUANT_MIN_M:
             return ("dequant", _prefill_plan_kw(lin, M))
-    if lin.kind == "fp8":
-        # M <= 16: the fp8 decode kernel (gemm_fp8.hip; forced waves / splitk are its own knobs); longer steps:
-        # fp8 -> bf16 scratch + the bf16 kernels on the Linear's prefill plan
+    if lin.kind in ("fp8", "mxfp4"):
+        # M <= 16: the fp8 / mxfp4 decode kernel (gemm_fp8.hip / gemm_mxfp4.hip; forced waves / splitk are its own
+        # knobs); longer steps: fp8 / mxfp4 -> bf16 scratch + the bf16 kernels on the Linear's prefill plan
         if row_idx is not None or ar is not None or norm_out is not None:
-            raise ValueError("fp8 Linear: no row_idx, fused all-reduce or norm hand-off")
+            raise ValueError(f"{lin.kind} Linear: no row_idx, fused all-reduce or norm hand-off")
         if M > 16:
             return ("dequant", _prefill_plan_kw(lin, M) if planned and path == PATH_AUTO else
                     dict(waves=waves, splitk=splitk, path=path))
@@ -167,7 +168,8 @@ def linear(x: torch.Tensor, lin: Linear, out: torch.Tensor | None = None,
     epi = EPI_QKV if qkv is not None else EPI_SILU if silu else EPI_F32 if out_f32 else EPI_BF16
     route = _gemm_route(lin, M, waves=waves, splitk=splitk, path=path, row_idx=row_idx, ar=ar, norm_out=norm_out)
     if route[0] == "dequant":
-        dq = _linear_fp8_dequant if lin.kind == "fp8" else _linear_awq_dequant
+        dq = (_linear_fp8_dequant if lin.kind == "fp8" else _linear_mxfp4_dequant if lin.kind == "mxfp4" else
+              _linear_awq_dequant)
         return dq(x, lin, out, residual, norm, qkv, epi, route[1])
     _, path, waves, splitk, ntb = route
     # (fault: the hand-off polls' word, at M > 16 the stream-K prefill kernel's bounded ticket poll)
@@ -181,11 +183,14 @@ def linear(x: torch.Tensor, lin: Linear, out: torch.Tensor | None = None,
         kw.update(awq_scales=lin.scales, awq_zeros=lin.zeros, group=lin.group)
         if lin.szp is not None:
             kw["awq_szp"] = lin.szp
-    if lin.kind == "fp8":
+    if lin.kind in ("fp8", "mxfp4"):
         if prenorm is not None:
-            raise ValueError("fp8 Linear: no norm hand-off")
-        kw["fp8_scales"] = lin.fscales
-        if attn is not None:  # the two-launch form: the fp8 kernel takes no fused-attention operands
+            raise ValueError(f"{lin.kind} Linear: no norm hand-off")
+        if lin.kind == "fp8":
+            kw["fp8_scales"] = lin.fscales
+        else:
+            kw["mxfp4_scales"] = lin.mscales
+        if attn is not None:  # the two-launch form: these kernels take no fused-attention operands
             C.gemm(x, lin.wp, lin.N, lin.K, out, epi, **kw)
             _attn_after(out, qkv, attn)
             return out
@@ -244,6 +249,18 @@ def _linear_fp8_dequant(x, lin: Linear, out, residual, norm, qkv, epi, plan_kw: 
     scratch = reserve_awq_scratch(x.device, lin.N * lin.K)[: lin.N * lin.K]
     gamma = norm[0] if norm is not None else None
     C.fp8_dequant(lin.wp, lin.fscales, lin.N, lin.K, scratch, gamma)
+    C.gemm(x, scratch, lin.N, lin.K, out, epi, bias=lin.bias, res=residual, ws=workspace(x.device),
+           **_norm_kw(norm, True), **_qkv_kw(qkv), **plan_kw)
+    return out
+
+
+def _linear_mxfp4_dequant(x, lin: Linear, out, residual, norm, qkv, epi, plan_kw: dict):
+    """MXFP4 step of M > 16 rows: e2m1 -> bf16 fragment-packed scratch (block scales and the RMSNorm gamma
+    folded in), then the bf16 kernels with the row-scale-only RMSNorm mode; the scratch is the AWQ path's."""
+    C = native()
+    scratch = reserve_awq_scratch(x.device, lin.N * lin.K)[: lin.N * lin.K]
+    gamma = norm[0] if norm is not None else None
+    C.mxfp4_dequant(lin.wp, lin.mscales, lin.N, lin.K, scratch, gamma)
     C.gemm(x, scratch, lin.N, lin.K, out, epi, bias=lin.bias, res=residual, ws=workspace(x.device),
            **_norm_kw(norm, True), **_qkv_kw(qkv), **plan_kw)
     return out
@@ -468,7 +485,7 @@ def softmax_scale(head_dim: int) -> float:
 __all__ = [
     "native", "native_available", "pack_weight", "unpack_weight", "interleave_gate_up", "pack_awq",
     "Linear", "linear", "attention", "workspace", "fault_word", "reset_handoffs",
-    "row_permutation", "reserve_awq_scratch", "pack_awq_sz", "pack_fp8", "unpack_fp8", "rmsnorm", "embedding", "rope_kv", "qk_norm_rope_kv", "attention_decode", "attention_prefill",
+    "row_permutation", "reserve_awq_scratch", "pack_awq_sz", "pack_fp8", "unpack_fp8", "pack_mxfp4", "unpack_mxfp4", "pack_mxfp4_scales", "unpack_mxfp4_scales", "mxfp4_dequant_ref", "rmsnorm", "embedding", "rope_kv", "qk_norm_rope_kv", "attention_decode", "attention_prefill",
     "prefill_tiles", "sample", "logprobs", "logprob_views", "softmax_scale", "ref", "host_device_copy", "tune_prefill", "apply_prefill_plans",
 ]
 

@@ -131,8 +131,8 @@ def tune_prefill(lins: list, ms: list[int], iters: int = 5, margin: float = TUNE
         plan = {}
         g = torch.Generator(device=dev)
         g.manual_seed(lin.N + lin.K)
-        # AWQ / FP8 layers run their long steps on a bf16 fragment-packed dequant scratch of the same
-        # shape (_linear_awq_dequant / _linear_fp8_dequant): time a random bf16 matrix in that layout
+        # AWQ / FP8 / MXFP4 layers run their long steps on a bf16 fragment-packed dequant scratch of the same shape
+        # (_linear_awq_dequant / _linear_fp8_dequant / _linear_mxfp4_dequant): time a random bf16 matrix in that layout
         wp = lin.wp if lin.kind == "dense" else pack_weight(
             (torch.rand(lin.N, lin.K, device=dev, generator=g) * 2 - 1).bfloat16())
         # the folded RMSNorm's row scale as in the step (qkv / gate_up: the x^2 sums ride in the K loop

@@ -98,7 +98,7 @@ class CustomAllReduce:
     def fuses(self, lin, x: torch.Tensor, out: torch.Tensor) -> bool:
         """Whether the row-parallel GEMM ``out = x @ lin^T`` can all-reduce in its epilogue
         (decode rows, bf16 output of at most AR_FUSED_TILES 16-column tiles on this device; dense and AWQ
-        Linears: the fp8 decode kernel has no all-reduce epilogue, its ranks all-reduce separately)."""
+        Linears: the fp8 and mxfp4 decode kernels have no all-reduce epilogue, their ranks all-reduce separately)."""
         return (self.fused and lin.kind in ("dense", "awq") and x.shape[0] <= 16 and out.dtype == torch.bfloat16 and out.device == self.device
                 and lin.N // 16 <= FUSED_TILES)
 
