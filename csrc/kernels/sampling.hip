@@ -18,6 +18,7 @@
 //   to {x_i > x_j} with fresh noise (if j is rejected, every token <= x_j is outside
 //   the nucleus too). So each rejection round costs one parallel pass; accepted
 //   samples are distributed exactly as the renormalised filtered distribution.
+//   -inf logits (masked tokens) are never drawn; a row with no finite logit returns token 0.
 // RNG: Philox4x32-10 keyed by the per-row seed, counter (float4 index, offset, round),
 // so results are reproducible for a given (seed, offset) and independent of NSEG.
 // Merges read the segments' partials in a fixed order: bit-reproducible.
@@ -152,6 +153,13 @@ __device__ __forceinline__ void sweep_range(const float4* x4, int v_lo, int v_hi
 }
 
 __device__ __forceinline__ void finish_row(const SampleArgs& a, int row, int chosen, float mx, float z, float c) {
+  if (mx == -INFINITY) {
+    // no finite logit in the row (everything masked): no argmax and no candidate, `chosen` is still
+    // acc_init()'s index sentinel. Token 0, as torch.argmax of such a row, and no logits read.
+    a.out[row] = 0;
+    if (a.out_logprob) a.out_logprob[row] = -INFINITY;
+    return;
+  }
   a.out[row] = chosen;
   if (a.out_logprob) a.out_logprob[row] = ((a.logits[(size_t)row * a.ldl + chosen] - mx) * c - log2f(z)) / LOG2E_S;
 }
